@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: env-steps/sec of the vectorised env.step() hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 With --gpus N > 1 and no torchrun environment, bench.py starts its own N ranks (one per GPU) as a child
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...` BEFORE touching
@@ -25,9 +25,13 @@ times eager launches only), so a short window is kernel-bound, not host-launch-b
 --rehearsals untimed-in-spirit passes first (host code paths warm; reported) and then --windows complete measured
 windows; before EVERY pass the W + K action buffers are refilled on the device with fresh random actions (same
 buffers, so the captured graph stays valid; untimed), so no pass replays an action it has seen.  `value` is the
-MEDIAN window (max over ranks per window); every window is listed in config.windows_ms_per_step.
+MEDIAN window (max over ranks per window); every window is listed in config.windows_ms_per_step.  A plain run times ONE
+window of exactly K steps (after 3 rehearsals while W + K <= REHEARSAL_MAX_STEPS, none beyond); --full defaults to
+15 windows after 3 rehearsals.  All untimed stepping is a fixed number of env-steps, so with the same arguments every run
+times the same actions from the same state; --dump-outputs DIR writes what the last timed step returned
+(dump_outputs).
 
-Rank 0 prints ONE JSON line (contract in the task statement) with extra objects:
+Rank 0 prints ONE JSON line (contract in the task statement); with --full it carries extra objects:
   roofline     -- what bounds the dominant kernel: top level `bound: "issue"`, `achieved` = `frac` = VALU issue
                   utilisation (VALU instructions per wavefront of the committed SQ profile x wavefronts per SIMD x 4
                   cycles over the kernel's average duration measured in THIS run with HIP events on the launch stream),
@@ -39,8 +43,9 @@ Rank 0 prints ONE JSON line (contract in the task statement) with extra objects:
   cpu_baseline -- the CPU oracle (plain-C port of the reference algorithm) timed on the host cores on bounded
                   samples: the headline workload on all usable cores and on one, BASELINE configs[0] (1 env,
                   DUMMY_TASK-equivalent, 1,000 random steps, 1 core) and configs[3] (flying); on rank 0 at every N;
+  config.api_* / config.fused_* -- the plain user loop through the public API, the fused rollouts;
   config.flying / config.cdm / config.small / config.facade_1env -- secondary measurements of the same window
-                  machinery in the default single-GPU run: BASELINE configs[3], the real IGLU targets with partial
+                  machinery in the single-GPU --full run: BASELINE configs[3], the real IGLU targets with partial
                   starting grids, configs[1] (4,096 envs) and configs[0] through the 1-env gym facade;
   config.sweep / config.large -- the headline workload at larger batches per GPU (envs per GPU is a tunable), the
                   largest (2,097,152 envs: beyond the Infinity Cache) with its own PMC profile: the HBM-bound regime.
@@ -64,6 +69,15 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md); ~6300 GB/s ach
 BYTES_BASE, BYTES_CHANGED = 1274, 1106
 GPU_CLOCK_GHZ = 2.4
 CDM_GOALS = os.path.join(ROOT, 'tests', 'golden', 'cdm_goals.npz')
+# A plain run rehearses the window only while that is cheap: the first passes cost tens of microseconds of cold host
+# code paths, a large share of a 20-step window and nothing of a long one.
+REHEARSAL_MAX_STEPS = 4096
+# Untimed stepping is counted in env-steps, not seconds, so that the state at the clock -- and what the timed steps
+# compute -- is the same in every run with the same arguments.  About 0.3 s (the clock ramp before the first pass) and
+# 2 ms (before every pass) of the fused walking rollout (~8e9 env-steps/s) and of eager flying steps (~4.5e9).
+RAMP_ENV_STEPS = {'walking': 2.4e9, 'flying': 1.35e9}
+PASS_ENV_STEPS = {'walking': 1.6e7, 'flying': 9e6}
+DUMP_MAX_BYTES = 64 << 20
 
 
 def parse_args(argv=None):
@@ -74,9 +88,16 @@ def parse_args(argv=None):
     ap.add_argument('--envs-per-gpu', type=int, default=ENVS_PER_GPU)
     ap.add_argument('--lanes-per-env', type=int, default=0)
     ap.add_argument('--seed', type=int, default=2024)
-    ap.add_argument('--windows', type=int, default=15, help='complete measured windows; value = their median')
-    ap.add_argument('--rehearsals', type=int, default=3,
-                    help='passes through the whole W + K sequence before the measured windows (reported, not counted)')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline window: 15 windows and 3 rehearsals by default, roofline, API loops, '
+                         'fused rollouts, secondary workloads, batch sweep, CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step returned (obs, reward, done) to DIR/<name>.npy')
+    ap.add_argument('--windows', type=int, default=None,
+                    help='complete measured windows; value = their median (default 1, with --full 15)')
+    ap.add_argument('--rehearsals', type=int, default=None,
+                    help='passes through the whole W + K sequence before the measured windows (reported, not counted; '
+                         f'default 3, without --full 0 when W + K > {REHEARSAL_MAX_STEPS})')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--cpu-sample-scale', type=float, default=1.0,
                     help='scales the CPU baseline\'s bounded samples (1.0 = about 25 s of CPU work; tests use 0.05)')
@@ -105,7 +126,12 @@ def parse_args(argv=None):
                     help='IGW_DIAG=1 only: timing-only ablation switches of the diagnostic library (results invalid)')
     ap.add_argument('--dry-run', action='store_true',
                     help='launcher / rendezvous check without a GPU: ranks reduce fake counters over gloo')
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.windows is None:
+        args.windows = 15 if args.full else 1
+    if args.rehearsals is None:
+        args.rehearsals = 3 if args.full or args.warmup + args.steps <= REHEARSAL_MAX_STEPS else 0
+    return args
 
 
 def _free_port():
@@ -374,8 +400,9 @@ class Runner:
             self.acts = torch.empty((W + K, N), dtype=torch.int32, device=device)
             self.act_t = list(self.acts.unbind(0))
         self.refill()
+        self.pass_env_steps = PASS_ENV_STEPS[mode]
         if not args.lockstep:
-            self.busy(0.0, MAX_STEPS)  # at least one episode length
+            self.busy(MAX_STEPS)  # at least one episode length
         self.graph, self.head, self.timed_as = None, K, 'eager env.step() calls'
         self.chains = max(1, int(getattr(args, 'chains', 1)))
         if not args.no_graph and K > 8:
@@ -397,11 +424,12 @@ class Runner:
             self.L.check(env.lib.igw_fill_actions_walking(env.ctx, self.acts.data_ptr(), self.acts.shape[0], t0, self.args.seed,
                                                           self.env_offset, env._stream()), 'igw_fill_actions_walking')
 
-    def busy(self, seconds, min_steps, fresh=True):
-        """Untimed stepping with FRESH random actions: the pre-roll to the steady state / the clock ramp."""
+    def busy(self, min_steps, env_steps=0, fresh=True):
+        """Untimed stepping with FRESH random actions: the pre-roll to the steady state / the clock ramp.  At least
+        `min_steps` steps per env and `env_steps` env-steps in all, whole chunks (a fixed amount of work, not of time)."""
         torch, env = self.torch, self.env
-        t_ramp, n_pre = time.perf_counter(), 0
-        while n_pre < min_steps or time.perf_counter() - t_ramp < seconds:
+        n_pre = 0
+        while n_pre < min_steps or n_pre * self.N < env_steps:
             if self.flying:   # (the first W + K actions of the buffers)
                 if fresh:
                     self.refill()
@@ -452,7 +480,7 @@ class Runner:
         # would run 2-3 % slower than in a long run.  So: about 2 ms of untimed stepping with fresh random actions
         # first (setup, like the pre-roll), then the contract's W warm-up steps and the clock.
         if not self.args.lockstep:
-            self.busy(0.002, 0, fresh=False)   # (the window refills the buffers right after)
+            self.busy(1, self.pass_env_steps, fresh=False)   # (the window refills the buffers right after)
         self.refill()
         # warm-up right before the clock; the counters are snapshotted on the device, not read, so nothing idles
         # the GPU between warm-up and clock
@@ -505,7 +533,7 @@ class Runner:
             ts = []
             for _ in range(reps):
                 if not self.args.lockstep:
-                    self.busy(0.002, 0, fresh=False)
+                    self.busy(1, self.pass_env_steps, fresh=False)
                 self.refill()
                 for t in range(self.W):
                     env.step(self.act_t[t])
@@ -541,12 +569,12 @@ class Runner:
         """`rehearsals` passes that are reported but not counted, then `windows` measured ones.  The first passes
         through the host code paths (Python bytecode, ctypes thunks, the HIP runtime's launch and graph-launch paths)
         cost 30-80 us more than later ones -- 10-20 % of a 20-step window and nothing to do with the step kernel.
-        Right before them 0.3 s of untimed stepping: task upload, graph capture and instantiation leave the GPU idle
-        for tens of milliseconds and its clocks drop."""
+        Right before them about 0.3 s of untimed stepping: task upload, graph capture and instantiation leave the GPU
+        idle for tens of milliseconds and its clocks drop."""
         from gridworld_amd import dist as gdist
         L, env, N, K = self.L, self.env, self.N, self.K
         if not self.args.lockstep:
-            self.busy(0.3, 0)
+            self.busy(1, RAMP_ENV_STEPS[self.mode])
         rehearsal_ms = [round(1e3 * self.window()[0] / K, 5) for _ in range(rehearsals)]
         walls, kernels, ps, resets, cells, counted, timelines = [], [], [], [], [], [], []
         import gc
@@ -769,6 +797,35 @@ def facade_rate(seed, steps=3000):
             'reference_python_here': 'BASELINE.md: 3.8-4.2 k steps/s step only, 2.9-3.2 k incl. resets (build container, 1 core)'}
 
 
+def dump_outputs(env, out_dir, max_envs=262144, max_grid_envs=8192, seed=0):
+    """--dump-outputs: what the last timed step handed its caller -- obs['agentPos' / 'inventory' / 'compass' / 'grid'],
+    reward, done -- as float32 arrays in out_dir/<name>.npy (exact: the grid and done are small integers).  64 MB at
+    most: beyond max_envs envs the per-env arrays, beyond max_grid_envs the grid (1,089 values per env), are written for
+    a fixed, seeded sample of envs, sorted; env_index.npy / grid_env_index.npy (float64) name the envs written."""
+    import numpy as np
+    import torch
+    N = env.num_envs
+
+    def sample(n):
+        idx = np.arange(N) if N <= n else np.sort(np.random.RandomState(seed).choice(N, n, replace=False))
+        return idx, torch.from_numpy(idx).to(env.device)
+
+    idx, idx_t = sample(max_envs)
+    gidx, gidx_t = sample(max_grid_envs)
+    arrays = {'agentPos': env.agent_pos[idx_t], 'inventory': env.inventory[idx_t], 'compass': env.compass[idx_t].unsqueeze(1),
+              'reward': env.reward[idx_t], 'done': env.done[idx_t], 'grid': env.grid[gidx_t]}
+    arrays = {k: v.to(torch.float32).cpu().numpy() for k, v in arrays.items()}
+    arrays['env_index'] = idx.astype(np.float64)
+    arrays['grid_env_index'] = gidx.astype(np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f'--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES} allowed')
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + '.npy'), a)
+    return {'dir': out_dir, 'files': sorted(k + '.npy' for k in arrays), 'bytes': total, 'envs': len(idx), 'grid_envs': len(gidx)}
+
+
 def main():
     args = parse_args()
     if args.gpus > 1 and 'RANK' not in os.environ:
@@ -808,7 +865,9 @@ def run(args):
     r = Runner(args, args.mode, args.workload, device, rank, world, node_barrier)
     env = r.env
     m = r.measure(args.windows, args.rehearsals)
+    dumped = dump_outputs(env, args.dump_outputs) if args.dump_outputs and rank == 0 else None
     max_elapsed = m['elapsed']
+    full = args.full
     # The one RCCL collective of the run (north star): every rank's DEVICE-SIDE step count of the median window --
     # the delta of IGW_STAT_STEPS, which every step launch adds its env count to (one atomic per launch) -- gathered over RCCL / xGMI; `value`
     # is computed from their sum, and the sum must be what the launches were asked to do.
@@ -821,8 +880,8 @@ def run(args):
                          f'per rank {steps_per_rank}, expected {N * K} per rank and window')
     ranks_seen = gdist.gather_counts(rank)   # (control plane)
     n_ranks = len(ranks_seen)
-    kernel_us_per_rank = [round(x, 3) for x in gdist.gather_floats(1e3 * m['kernel_ms'])]   # (control plane)
-    api = r.api_loops() if not args.no_api else None
+    kernel_us_per_rank = [round(x, 3) for x in gdist.gather_floats(1e3 * m['kernel_ms'])] if full else None   # (control plane)
+    api = r.api_loops() if full and not args.no_api else None
     # the same window with the captured steps as P independent chains of sub-batch launches (parallel graph branches)
     chain_sweep = {}
     if world == 1 and args.chain_sweep and not args.no_graph and K > 8:
@@ -843,7 +902,7 @@ def run(args):
 
     # secondary: fused T-step rollout (state resident in LDS/registers, in-kernel RNG)
     fused = fused_rec = None
-    if not args.no_fused and not flying:
+    if full and not args.no_fused and not flying:
         Tf = 250
         env.rollout(Tf, seed=args.seed + 1, t0=0, env_offset=r.env_offset)  # warm
         torch.cuda.synchronize(device)
@@ -867,7 +926,7 @@ def run(args):
         r_steps, r_el = gdist.reduce_window(N * Tr, time.perf_counter() - t0)
         fused_rec = r_steps / r_el
 
-    if flying and not args.no_fused:   # the fused loop over the recorded flying actions (igw_rollout_flying_actions)
+    if full and flying and not args.no_fused:   # the fused loop over the recorded flying actions (igw_rollout_flying_actions)
         rec = r.acts
         Tr = r.acts['movement'].shape[0]
         env.rollout_actions(rec)  # warm
@@ -908,13 +967,13 @@ def run(args):
         del subs
 
     lanes = env.cfg.lanes_per_env or auto_lanes(N)
-    roof, iss = roofline_of(r, m, lanes, has_start_frac=0.96 if args.workload == 'cdm' else 0.0)
+    roof, iss = roofline_of(r, m, lanes, has_start_frac=0.96 if args.workload == 'cdm' else 0.0) if full else (None, None)
     timed_as = r.timed_as
 
     # secondaries of the default single-GPU run: BASELINE configs[3] (flying) and the real IGLU targets with partial
     # starting grids, through the same window machinery (fewer windows)
     secondary = {}
-    if world == 1 and not args.no_secondary and not flying and args.workload == 'rt20' and not args.debug_flags:
+    if full and world == 1 and not args.no_secondary and not flying and args.workload == 'rt20' and not args.debug_flags:
         del r, env
         torch.cuda.empty_cache()
         for key, mode, wl in (('flying', 'flying', 'rt20'), ('cdm', 'walking', 'cdm')):
@@ -941,7 +1000,7 @@ def run(args):
     # the latency end: BASELINE configs[1] (4,096 envs, DUMMY_TASK-equivalent, gym.make defaults) through the same
     # window machinery, and configs[0] through the 1-env gym facade
     small = facade = None
-    if world == 1 and not args.no_secondary and not flying and args.workload == 'rt20' and not args.debug_flags:
+    if full and world == 1 and not args.no_secondary and not flying and args.workload == 'rt20' and not args.debug_flags:
         Ns = 4096
         r3 = Runner(args, 'walking', 'dummy', device, rank, world, node_barrier, N=Ns)
         m3 = r3.measure(max(3, args.windows // 2), 2)
@@ -968,7 +1027,7 @@ def run(args):
     # (profiles/r*_large_traffic.json): the one regime in which the HBM roofline is the roofline.
     sweep = large = None
     sizes = []
-    if world == 1 and not args.no_secondary and not flying and args.workload == 'rt20' and not args.debug_flags and args.sweep:
+    if full and world == 1 and not args.no_secondary and not flying and args.workload == 'rt20' and not args.debug_flags and args.sweep:
         sizes = sorted({int(x) for x in args.sweep.split(',') if x.strip()} - {N})
     if sizes:
         sweep = {str(N): {'value': N * K / max_elapsed, 'ms_per_step': 1e3 * max_elapsed / K, 'kernel_us': 1e3 * m['kernel_ms'],
@@ -1036,23 +1095,28 @@ def run(args):
                    'windows_kernel_us': m['windows_kernel_us'],
                    'episodes': 'lock-step' if args.lockstep else 'de-synchronised (random episode phase + pre-roll)',
                    'setup': 'untimed: task upload, pre-roll of >= 250 steps with fresh random actions (steady state), graph '
-                            'capture + one replay, 0.3 s more of such stepping (clock ramp), %d rehearsal passes (host code '
-                            'paths warm; reported, not counted); before every pass 2 ms of such stepping (the clocks drop while the host '
-                            'reads counters between passes) and a refill of the W + K action buffers on the device with fresh random '
-                            'actions' % args.rehearsals,
+                            'capture + one replay, about 0.3 s more of such stepping (clock ramp; a fixed number of env-steps), '
+                            '%d rehearsal passes (host code paths warm; reported, not counted); before every pass about 2 ms of '
+                            'such stepping (the clocks drop while the host reads counters between passes) and a refill of the '
+                            'W + K action buffers on the device with fresh random actions' % args.rehearsals,
                    'rehearsal_ms_per_step': m['rehearsal_ms_per_step'],
                    'resets_in_window': m['resets_in_window'], 'p_changed': m['p_changed'],
                    'p_cell_changed': m['p_cell_changed'],
                    'step_count_gather': gather_via, 'device_step_counts_per_rank': steps_per_rank,
-                   'ranks_seen': ranks_seen, 'kernel_us_per_rank': kernel_us_per_rank,
+                   'ranks_seen': ranks_seen,
                    'host': {'usable_cpus': usable_cpus(), 'torch_threads': torch.get_num_threads()},
-                   'fused_rollout_env_steps_per_s': fused,
-                   'fused_rollout_recorded_actions_env_steps_per_s': fused_rec,
-                   'chains': chains_used,
-                   'overlap_note': 'concurrent sub-batch launches (two streams, parallel graph branches, one graph per stream) are '
-                                   'all slower than one whole-batch launch per step on this part: profiles/r05_chains.txt'},
-        'roofline': roof,
+                   'chains': chains_used},
     }
+    if dumped is not None:
+        out['config']['outputs'] = dumped
+    if full:
+        out['config'].update({
+            'kernel_us_per_rank': kernel_us_per_rank,
+            'fused_rollout_env_steps_per_s': fused,
+            'fused_rollout_recorded_actions_env_steps_per_s': fused_rec,
+            'overlap_note': 'concurrent sub-batch launches (two streams, parallel graph branches, one graph per stream) are '
+                            'all slower than one whole-batch launch per step on this part: profiles/r05_chains.txt'})
+        out['roofline'] = roof
     if api is not None:
         head = out['value'] / n_ranks   # this rank's share: the API loops are per rank, not reduced
         out['config']['api_step_env_steps_per_s'] = api['eager']
@@ -1082,7 +1146,7 @@ def run(args):
         out['config']['facade_1env'] = facade
     if iss is not None:
         out['issue'] = iss
-    if not args.no_cpu_baseline:
+    if full and not args.no_cpu_baseline:
         # on rank 0 at every N (north star: "next to the reference CPU path timed on the node's own host cores ... in the
         # same run").  The windows are over; with N > 1 the other ranks have returned and wait in the closing gloo barrier
         # (blocked in a socket read, not spinning), so rank 0 has the node's granted cores for the sample.

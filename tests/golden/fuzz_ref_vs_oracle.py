@@ -27,7 +27,7 @@ and the reset observation / internals at every reset.  A scenario draws
 
     python tests/golden/fuzz_ref_vs_oracle.py --scenarios 20000 --procs 8 --out profiles/r05_fuzz_ref_vs_oracle.json
 
-tests/test_ref_fuzz.py runs a 200-scenario slice of this when /root/reference exists.  The scenario generator itself
+tests/test_ref_fuzz.py replays a 200-scenario slice of this, recorded by tests/golden/gen_ref_fuzz.py.  The scenario generator itself
 is tests/scenario_fuzz.py, shared with the product-side run of the SAME seeds on the GPU (tests/test_gpu_facade_fuzz.py:
 gridworld_amd.make(...) against the oracle).
 """

@@ -60,7 +60,7 @@ def test_two_ranks_through_torchrun_on_one_shared_gpu():
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_PORT'):
         env.pop(k, None)
     n, k = 8192, 20
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', str(k), '--warmup', '5', '--envs-per-gpu', str(n),
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--gpus', '2', '--steps', str(k), '--warmup', '5', '--envs-per-gpu', str(n),
            '--windows', '3', '--rehearsals', '1', '--cpu-sample-scale', '0.05', '--no-secondary', '--no-api', '--no-fused', '--no-async']
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-500:], r.stderr[-3000:])

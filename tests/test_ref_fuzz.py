@@ -1,25 +1,33 @@
-"""Reference <-> oracle randomised slice (build container only: needs /root/reference; skipped on the GPU box).
+"""Reference <-> oracle randomised slice, from the reference's recorded side (no reference needed at test time).
 
-200 fresh scenarios of tests/golden/fuzz_ref_vs_oracle.py -- random create_env kwargs, task sources (Task,
-Subtasks, CustomTasks, RandomTasks), starting grids, initialize_world poses, all three action spaces, glibc and
-correctly rounded trig -- stepped in lock-step through the imported Python reference and the CPU oracle; every
-observation, reward, done, grid, float64 internal and task counter must agree on every step.  The long run
-(>= 5 M reference steps) is logged in profiles/r05_fuzz_ref_vs_oracle.json."""
+200 scenarios of tests/scenario_fuzz.py (seeds 77000-77199, at most 150 steps) -- random create_env kwargs, task
+sources (Task, Subtasks, CustomTasks, RandomTasks), starting grids, initialize_world poses, all three action spaces,
+glibc and correctly rounded trig -- whose reference side tests/golden/gen_ref_fuzz.py recorded into
+tests/golden/s13_ref_fuzz.npz: every observation, reward, done, float64 internal and task counter the imported Python
+reference returned, and the task it held at every reset.  The CPU oracle is stepped live through the same scenarios
+and must agree on every step (tests/ref_fuzz_replay.py serves the records in the order run_scenario reads them).
+The live version is tests/golden/fuzz_ref_vs_oracle.py; its long run (>= 5 M reference steps) is logged in
+profiles/r05_fuzz_ref_vs_oracle.json."""
 import os
-import sys
 
-import pytest
+import numpy as np
+
+import ref_fuzz_replay as R
+import scenario_fuzz as S
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
-pytestmark = pytest.mark.skipif(not os.path.isdir('/root/reference'),
-                                reason='the Python reference only exists in the build container')
-
 
 def test_reference_vs_oracle_200_scenarios():
-    sys.path.insert(0, os.path.join(HERE, 'golden'))
-    import fuzz_ref_vs_oracle as F
-    s = F.run(range(77000, 77200), procs=min(4, os.cpu_count() or 1), max_T=150)   # (scenario generator: tests/scenario_fuzz.py)
+    goals = list(np.load(os.path.join(HERE, 'golden', 'cdm_goals.npz'))['dense'])   # sorted C1..C157, as the reference's
+    B = R.ReplayBackend(os.path.join(HERE, 'golden', 's13_ref_fuzz.npz'), goals)
+    assert B.seeds() == list(range(77000, 77200))
+    results = []
+    for seed in B.seeds():
+        B.select(seed)
+        results.append(S.run_scenario_safe(seed, B, max_T=150))
+        assert results[-1]['mismatch'] is not None or B.replayed_all(), seed
+    s = S.summarize(results, 0.0)
     assert s['scenarios'] == 200 and s['reference_env_steps'] > 15000
     assert s['mismatches'] == 0, s['first_mismatches'][:2]
     # every scenario family was drawn

@@ -17,7 +17,7 @@ for wl in "walking rt20" "walking cdm" "flying rt20"; do
   set -- $wl
   for rep in 1 2 3; do
     for i in 0 1 2 3 4; do
-      IGW_AB_NO_STEP_COUNTER=1 IGW_LIB=$PWD/gridworld_amd/libigw_ab$i.so python3 bench.py --no-cpu-baseline --no-fused --no-secondary --no-api --mode $1 --workload $2 --steps ${STEPS:-400} --warmup 20 --windows 3 --rehearsals 1 2>/dev/null | python3 -c "
+      IGW_AB_NO_STEP_COUNTER=1 IGW_LIB=$PWD/gridworld_amd/libigw_ab$i.so python3 bench.py --full --no-cpu-baseline --no-fused --no-secondary --no-api --mode $1 --workload $2 --steps ${STEPS:-400} --warmup 20 --windows 3 --rehearsals 1 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads([l for l in sys.stdin.read().strip().splitlines() if l.startswith('{')][-1]); print('rep $rep variant $i [${VARS[$i]}] $1 $2 kernel %.3f us  %.3f G  %s' % (d['roofline']['kernel_avg_ms']*1e3, d['value']/1e9, d['config']['windows_kernel_us']))"
     done
