@@ -106,12 +106,15 @@ class GridWorld:
 
     def __init__(self, render=True, max_steps=250, select_and_place=False, discretize=False, right_placement_scale=1.,
                  wrong_placement_scale=0.1, render_size=(64, 64), target_in_obs=False, action_space='walking',
-                 vector_state=True, fake=False, name='', device='cuda:0'):
-        if render and not fake:
-            raise NotImplementedError('the renderer is out of scope of the MI355X step path; pass render=False '
-                                      "(or use 'IGLUGridworldVector-v0')")
+                 vector_state=True, fake=False, name='', device='cuda:0', renderer=None):
+        if renderer not in (None, 'hip'):
+            raise ValueError(f"unknown renderer {renderer!r}; the one renderer is 'hip'")
+        if render and not fake and renderer is None:
+            raise NotImplementedError("render=True needs renderer='hip' (the batched HIP ray caster of the "
+                                      "first-person frame); or pass render=False (or use 'IGLUGridworldVector-v0')")
         self.vector_state, self.target_in_obs, self.fake, self.do_render = vector_state, target_in_obs, fake, render
         self.render_size, self.name = render_size, name
+        self.renderer_kind = renderer
         self.max_steps, self.select_and_place, self.discretize = max_steps, select_and_place, discretize
         self.action_space_type = action_space
         # kept with the caller's types: the reference's reward is `int * scale` (env.py:293-296), a Python int
@@ -122,7 +125,7 @@ class GridWorld:
         self._vec = VecGridWorld(1, device=device, action_space=action_space, select_and_place=select_and_place,
                                  size_reward=False, max_steps=max_steps, right_placement_scale=right_placement_scale,
                                  discretize=discretize, wrong_placement_scale=wrong_placement_scale, num_tasks=1,
-                                 host_records=True)
+                                 host_records=True, render_size=render_size)
         self._task = None
         self._task_generator = None
         self._overwrite_starting_grid = None
@@ -192,11 +195,28 @@ class GridWorld:
         else:
             self._step_call = lambda: v.lib.igw_step_walking(v.ctx, p, self._stream_handle)
         self._read_back()   # a fresh Agent (core/world.py:12-29): inventory 20 x 6, BLUE active, time_int_steps 2
+        # the first-person frame (renderer='hip'): RGBA [H, W, 4] in pinned, device-mapped host memory, rendered on the
+        # env's stream right behind the step (one more launch, the same synchronisation)
+        self._frame = None
+        if self.renderer_kind == 'hip':
+            W, H = int(self.render_size[0]), int(self.render_size[1])
+            self._frame = torch.zeros((1, H, W, 4), dtype=torch.uint8).pin_memory()
+
+    def _launch_frame(self):
+        from . import render as R
+        v = self._vec
+        R.render_into(v.agent_buf.data_ptr(), v.grid_buf.data_ptr(), v.occ_buf.data_ptr(), 1, v._atlas(),
+                      self._frame.data_ptr(), self._frame.shape[2], self._frame.shape[1], 4, self._stream_handle)
+
+    def _renders(self):
+        return self.do_render and not self.fake and self._frame is not None
 
     def _device_step(self):
         rc = self._step_call()
         if rc:
             L.check(rc, 'igw_step (facade)')
+        if self._renders():
+            self._launch_frame()
         self._stream.synchronize()
 
     def _read_back(self):
@@ -272,6 +292,10 @@ class GridWorld:
         self._task.reset()
         self._upload_task()
         self._vec.reset()
+        if self._renders():
+            self._stream.wait_stream(torch.cuda.current_stream(self._vec.device))
+            self._launch_frame()
+            self._stream.synchronize()
         # GridWorld.max_int (env.py:241): the user task -- full_grid admissibility included -- on the starting grid
         meta = self._vec.task_meta[0, 42:44]
         self._read_back()
@@ -294,7 +318,9 @@ class GridWorld:
             obs['agentPos'] = f[0:5].copy()
         if self.target_in_obs:
             obs['target_grid'] = np.asarray(self._task.target_grid).copy().astype(np.int32)
-        if self.do_render:
+        if self._renders():   # env.py:258, 300: render()[..., :-1]
+            obs['pov'] = self._frame[0, ..., :3].numpy().copy()
+        elif self.do_render:
             obs['pov'] = self.observation_space['pov'].sample()
         return obs
 
@@ -342,7 +368,27 @@ class GridWorld:
         return obs, reward, bool(self._host['out'][52]), {}
 
     def render(self):
-        raise ValueError('create env with render=True')
+        """Renderer.render() (gridworld/render.py:129-144): the current frame as RGBA uint8 [H, W, 4], row 0 on top."""
+        if not self._renders():
+            raise ValueError('create env with render=True')
+        self._stream.wait_stream(torch.cuda.current_stream(self._vec.device))
+        self._launch_frame()
+        self._stream.synchronize()
+        return self._frame[0].numpy().copy()
+
+    def enable_renderer(self):
+        """env.py:119-136: switches the frame on for an env created with render=False (it resets the env first, as
+        the reference does).  Needs renderer='hip' at construction."""
+        if self.fake or self._renders():
+            return
+        if self.renderer_kind is None:
+            raise NotImplementedError("enable_renderer needs an env created with renderer='hip'")
+        self.reset()
+        self.do_render = True
+
+    def set_render_atlas(self, atlas):
+        """The texture atlas of the frame (VecGridWorld.set_render_atlas), e.g. render.load_atlas('texture.png')."""
+        self._vec.set_render_atlas(atlas)
 
 
 class Wrapper:
@@ -396,12 +442,12 @@ class SizeReward(Wrapper):
 
 def create_env(render=True, discretize=True, size_reward=True, select_and_place=True, right_placement_scale=1,
                render_size=(64, 64), target_in_obs=False, vector_state=False, max_steps=250, action_space='walking',
-               wrong_placement_scale=0.1, name='', fake=False, device='cuda:0'):
-    """gridworld/env.py:333-350 (same defaults)."""
+               wrong_placement_scale=0.1, name='', fake=False, device='cuda:0', renderer=None):
+    """gridworld/env.py:333-350 (same defaults); renderer='hip' makes render=True draw the first-person frame."""
     env = GridWorld(render=render, select_and_place=select_and_place, discretize=discretize,
                     right_placement_scale=right_placement_scale, wrong_placement_scale=wrong_placement_scale, name=name,
                     render_size=render_size, target_in_obs=target_in_obs, vector_state=vector_state, max_steps=max_steps,
-                    action_space=action_space, fake=fake, device=device)
+                    action_space=action_space, fake=fake, device=device, renderer=renderer)
     if size_reward:
         env = SizeReward(env)
     return env

@@ -34,7 +34,8 @@ class Box(Space):
 
     def sample(self):
         if np.issubdtype(self.dtype, np.integer):
-            return np.random.randint(self.low, self.high + 1).astype(self.dtype)
+            # bounds widened first: high + 1 overflows the box's own dtype at its maximum (uint8 255 for 'pov')
+            return np.random.randint(self.low.astype(np.int64), self.high.astype(np.int64) + 1).astype(self.dtype)
         return np.random.uniform(self.low, self.high).astype(self.dtype)
 
     def contains(self, x):

@@ -36,7 +36,8 @@ class VecGridWorld:
     def __init__(self, num_envs, device='cuda:0', action_space='walking', select_and_place=True,
                  size_reward=True, max_steps=250, right_placement_scale=1., wrong_placement_scale=0.1,
                  discretize=True, autoreset=False, num_tasks=None, lanes_per_env=0, debug_flags=0, env_index_base=0,
-                 host_records=False, render=False, render_size=(64, 64), target_in_obs=False, vector_state=True, name='', fake=False):
+                 host_records=False, render=False, render_size=(64, 64), target_in_obs=False, vector_state=True, name='', fake=False,
+                 renderer=None):
         """create_env's keyword arguments (gridworld/env.py:333-338) plus the batch's own: num_envs, device,
         autoreset (reset inside step), num_tasks (rows of the task table, default num_envs), lanes_per_env
         (0 = automatic), env_index_base (global index of env 0: rank / sub-batch offset), debug_flags (IGW_DIAG
@@ -44,9 +45,15 @@ class VecGridWorld:
         kernels read and write across PCIe: a host-side consumer of a FEW envs -- the 1-env gym facade -- then needs no
         copy at all, only a stream synchronisation; the observation tensors are CPU tensors in that case).  Anything else is a TypeError, as in create_env.  render / render_size / fake / name /
         target_in_obs / vector_state are accepted for signature compatibility: this is the render=False,
-        vector_state=True path (observations are the state tensors; `targets()` gives the target grids)."""
-        if render and not fake:
-            raise NotImplementedError('the renderer is out of scope of the MI355X step path; pass render=False')
+        vector_state=True path (observations are the state tensors; `targets()` gives the target grids).
+        renderer='hip' adds the reference's first-person frame: reset() / step() also return obs['pov'], a uint8
+        [N, H, W, 3] device tensor (W, H = render_size) rendered by libigw_render.so on the same stream after the
+        step / reset launch, the same tensor every call (render_pov(), DESIGN.md "First-person frames")."""
+        if renderer not in (None, 'hip'):
+            raise ValueError(f"unknown renderer {renderer!r}; the one renderer is 'hip'")
+        if render and not fake and renderer is None:
+            raise NotImplementedError("render=True needs renderer='hip' (the batched HIP ray caster of the "
+                                      "first-person frame); or pass render=False")
         if not torch.cuda.is_available():
             raise L.IgwError('VecGridWorld needs a HIP device (no CPU fallback)')
         if action_space not in ('walking', 'flying'):
@@ -107,6 +114,11 @@ class VecGridWorld:
         # bumped by every call that changes what a step LAUNCH is given by value (the kernel parameters: sampler
         # settings, the episode-log buffers): a captured StepGraph carries the values of its capture
         self.config_epoch = 0
+        self.render_size = (int(render_size[0]), int(render_size[1]))
+        self._render_atlas = None
+        self.pov = None   # obs['pov'] of renderer='hip': [N, H, W, 3], rewritten by every reset / step
+        if renderer == 'hip':
+            self.pov = torch.empty((N, self.render_size[1], self.render_size[0], 3), dtype=torch.uint8, device=dev)
 
     def __del__(self):
         ctx = getattr(self, 'ctx', None)
@@ -120,7 +132,10 @@ class VecGridWorld:
         They are NOT dense [N] tensors: agent_pos [N,5], inventory [N,6], compass [N], reward [N] are float32 views
         with a row stride of 16 elements (the 64-byte output record), done [N] is uint8 with stride 64, env_task /
         episode int32 with stride 4, grid [N,9,11,11] int8 with row stride 1104.  A consumer that needs packed
-        memory (.view(), DLPack, a custom kernel indexing [i]) takes `dense()` or calls .contiguous()."""
+        memory (.view(), DLPack, a custom kernel indexing [i]) takes `dense()` or calls .contiguous().
+        The first-person frame (renderer='hip', render_pov) is rendered from this same state, so it follows the same
+        convention as `grid`: after a step that ended an episode of an auto-reset env, the frame shows the NEW
+        episode's first state (the pose and grid the reset wrote), not the last state of the finished one."""
         N = self.num_envs
         f = self.out_buf.view(torch.float32)          # [N, 16]
         self.agent_pos = f[:, 0:5]                    # x, y, z, pitch, yaw
@@ -295,6 +310,8 @@ class VecGridWorld:
         L.check(self.lib.igw_reset(self.ctx, None if m is None else C.c_void_p(m.data_ptr()),
                                    L.RESET_KEEP_SIZE if keep_size else 0, self._stream()), 'igw_reset')
         self._mask_keep = m
+        if self.pov is not None:
+            return self._with_pov(self.obs())
         return self.obs()
 
     @staticmethod
@@ -333,6 +350,8 @@ class VecGridWorld:
             if rc:
                 L.check(rc, 'igw_step_walking')
             self._act_keep = a
+            if self.pov is not None:
+                return self._with_pov(self._obs.copy()), self.reward, self.done, {}
             return self._obs.copy(), self.reward, self.done, {}
         dev = self.device
         self._check_camera(actions['camera'])
@@ -366,7 +385,37 @@ class VecGridWorld:
             if rc:
                 L.check(rc, 'igw_step_flying')
             self._act_keep = (mv, cam, inv, pl)
+        if self.pov is not None:
+            return self._with_pov(self._obs.copy()), self.reward, self.done, {}
         return self._obs.copy(), self.reward, self.done, {}
+
+    # ---- first-person frames (libigw_render.so, include/igw_render.h) ----
+    def _with_pov(self, obs):
+        self.render_pov(out=self.pov)
+        obs['pov'] = self.pov
+        return obs
+
+    def set_render_atlas(self, atlas):
+        """The texture atlas of render_pov: uint8 [S, S, 4] (numpy or tensor, row 0 = the top image row), S a multiple
+        of 8 up to 256 -- e.g. render.load_atlas('texture.png') of the reference for its look.  Default: the flat-colour
+        atlas of render.default_atlas()."""
+        from . import render as R
+        a = R.check_atlas(atlas.cpu().numpy() if torch.is_tensor(atlas) else atlas)
+        self._render_atlas = torch.from_numpy(a).to(self.device)
+
+    def _atlas(self):
+        if self._render_atlas is None:
+            from . import render as R
+            self._render_atlas = torch.from_numpy(R.default_atlas()).to(self.device)
+        return self._render_atlas
+
+    def render_pov(self, out=None, channels=3, size=None):
+        """The first-person frame of every env's CURRENT state (see _make_views for auto-reset envs): uint8
+        [N, H, W, channels] with W, H = size (default render_size), row 0 the top image row, channels 3 (RGB) or 4 (RGBA,
+        what the reference's Renderer.render() returns).  One launch on the current stream; with `out` (a contiguous
+        uint8 device tensor of that shape) nothing is allocated, so the call can be captured in a graph."""
+        return _render_rows(self, self.agent_buf, self.grid_buf, self.occ_buf, self.num_envs, out, channels, size,
+                            self._stream())
 
     # ---- a captured step loop (the loop of examples/run_env.py:18-26 as ONE HIP-graph launch) ----
     def capture_steps(self, actions, record=False, chains=1):
@@ -642,6 +691,8 @@ class SubBatch:
         self.agent_pos, self.inventory = parent.agent_pos[sl], parent.inventory[sl]
         self.compass, self.reward, self.done = parent.compass[sl], parent.reward[sl], parent.done[sl]
         self.grid = parent.grid[sl]
+        self.render_size = parent.render_size
+        self.pov = None if parent.pov is None else parent.pov[sl]
         self._inherit_sampling()
 
     def _inherit_sampling(self):
@@ -660,8 +711,23 @@ class SubBatch:
             self.ctx = None
 
     def obs(self):
-        return {'agentPos': self.agent_pos, 'inventory': self.inventory, 'compass': self.compass.unsqueeze(1),
-                'grid': self.grid}
+        o = {'agentPos': self.agent_pos, 'inventory': self.inventory, 'compass': self.compass.unsqueeze(1),
+             'grid': self.grid}
+        if self.pov is not None:
+            o['pov'] = self.pov
+        return o
+
+    def _atlas(self):
+        return self.parent._atlas()
+
+    def render_pov(self, out=None, channels=3, size=None):
+        """VecGridWorld.render_pov for this sub-batch's rows, on its own stream."""
+        sl = slice(self.lo, self.lo + self.num_envs)
+        p = self.parent
+        if out is not None:
+            out.record_stream(self.stream)
+        return _render_rows(self, p.agent_buf[sl], p.grid_buf[sl], p.occ_buf[sl], self.num_envs, out, channels, size,
+                            C.c_void_p(self.stream.cuda_stream), stream_obj=self.stream)
 
     def step_walking_ptr(self, actions_i32):
         """actions_i32: contiguous int32 device tensor [n]; launched on this sub-batch's stream (the tensor is
@@ -671,9 +737,13 @@ class SubBatch:
         actions_i32.record_stream(self.stream)
         L.check(self.lib.igw_step_walking(self.ctx, actions_i32.data_ptr(), C.c_void_p(self.stream.cuda_stream)),
                 'igw_step_walking')
+        if self.pov is not None:
+            self.render_pov(out=self.pov)
 
     def reset(self):
         L.check(self.lib.igw_reset(self.ctx, None, 0, C.c_void_p(self.stream.cuda_stream)), 'igw_reset')
+        if self.pov is not None:
+            self.render_pov(out=self.pov)
         return self.obs()
 
     def synchronize(self):
@@ -682,6 +752,28 @@ class SubBatch:
     def join(self):
         """Orders the current stream after everything queued on this sub-batch (no host wait)."""
         torch.cuda.current_stream(self.device).wait_stream(self.stream)
+
+
+def _render_rows(env, agent, grid, occ, n, out, channels, size, stream, stream_obj=None):
+    """igw_render_pov over rows of a batch's state buffers (a whole VecGridWorld or a SubBatch's slice)."""
+    from . import render as R
+    if channels not in (3, 4):
+        raise ValueError(f'channels must be 3 or 4, got {channels}')
+    W, H = (int(size[0]), int(size[1])) if size is not None else env.render_size
+    shape = (n, H, W, channels)
+    if out is None:
+        if stream_obj is not None:
+            with torch.cuda.stream(stream_obj):
+                out = torch.empty(shape, dtype=torch.uint8, device=env.device)
+        else:
+            out = torch.empty(shape, dtype=torch.uint8, device=env.device)
+    elif (tuple(out.shape) != shape or out.dtype != torch.uint8 or not out.is_contiguous()
+          or out.device != env.device):
+        raise ValueError(f'out must be a contiguous uint8 tensor {shape} on {env.device}, got '
+                         f'{out.dtype} {tuple(out.shape)} on {out.device}')
+    R.render_into(agent.data_ptr(), grid.data_ptr(), occ.data_ptr(), n, env._atlas(), out.data_ptr(), W, H, channels,
+                  stream)
+    return out
 
 
 def task_eval(targets, grids, full_grids=None, invariant=None, device='cuda:0'):
