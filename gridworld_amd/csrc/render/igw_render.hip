@@ -9,35 +9,14 @@
 // and grid go to LDS once per block, the camera basis is built once per block in f64 (like the pose it comes from)
 // and rounded to f32; every pixel then works in f32 relative to an integer origin next to the eye (all cell and
 // ground-quad boundaries are exact half-integers there).  Colours are staged in LDS and leave as 16-byte stores.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
 #include <stdio.h>
 
-#include "../../../include/igw_render.h"
+#include "igw_render_frame.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kChunk = 4096;           // pixels per block: one block per env at 64 x 64
-constexpr int kGridStride = 1104;      // include/igw.h: IGW_GRID_STRIDE
-constexpr int kOccWords = 48;          // include/igw.h: IGW_OCC_WORDS
 constexpr int kAgentBytes = 64;        // include/igw.h: IGW_AGENT_BYTES
-constexpr float kNear = 0.1f, kFar = 30.f;   // gluPerspective(90, W/H, 0.1, 30), gridworld/render.py:104
-
-// the six faces of a cube, by the side the ray enters through (gridworld/utils.py:26-43 names)
-enum Face { kTop, kBottom, kLeft, kRight, kFront, kBack };
-
-__device__ __forceinline__ bool occupied(const uint32_t* occ, int cy, int cx, int cz) {
-    // include/igw.h: bit (y+1)*169 + (x+6)*13 + (z+6) for world (x, y, z) = grid[y+1][x+5][z+5]
-    const int bit = cy * 169 + (cx + 1) * 13 + (cz + 1);
-    return (occ[bit >> 5] >> (bit & 31)) & 1u;
-}
-
-__device__ __forceinline__ int texel_index(float u, int n) {   // GL_NEAREST texel of coordinate u in [0, 1] on n texels
-    int k = (int)floorf(u * (float)n);
-    return k < 0 ? 0 : k >= n ? n - 1 : k;
-}
+constexpr int kTrajBytes = 64;         // include/igw.h: IGW_TRAJ_BYTES
 
 __global__ __launch_bounds__(kThreads) void igw_render_pov_kernel(const uint8_t* __restrict__ agent,
                                                               const int8_t* __restrict__ grid,
@@ -53,160 +32,68 @@ __global__ __launch_bounds__(kThreads) void igw_render_pov_kernel(const uint8_t*
         s_grid4[tid] = reinterpret_cast<const uint4*>(grid + env * kGridStride)[tid];
     else if (tid >= 128 && tid < 128 + kOccWords / 4)
         s_occ4[tid - 128] = reinterpret_cast<const uint4*>(occ + env * kOccWords)[tid - 128];
-
-    // camera (gridworld/render.py:94-111): forward = get_sight_vector, right, up; f64 like the pose
     const double* pose = reinterpret_cast<const double*>(agent + env * kAgentBytes);
-    const double ex = pose[0], ey = pose[1], ez = pose[2];
-    double sy, cy, sp, cp;
-    sincos(pose[3] * (M_PI / 180.0), &sy, &cy);
-    sincos(pose[4] * (M_PI / 180.0), &sp, &cp);
-    const float fx = (float)(sy * cp), fy = (float)sp, fz = (float)(-cy * cp);
-    const float rx = (float)cy, rz = (float)sy;
-    const float ux = (float)(-sy * sp), uy = (float)cp, uz = (float)(cy * sp);
-    // a pose that is not finite or far outside the world sees nothing but sky (the scene spans |x|, |z| <= 18.5)
-    const bool visible = fabs(ex) < 1e4 && fabs(ey) < 1e4 && fabs(ez) < 1e4 && isfinite(fx + fy + fz + ux + uy + uz);
-    // integer origin next to the eye: eye in [0, 1)^3, cell / quad boundaries exact
-    const double oxd = visible ? floor(ex) : 0., oyd = visible ? floor(ey) : 0., ozd = visible ? floor(ez) : 0.;
-    const int ox = (int)oxd, oy = (int)oyd, oz = (int)ozd;
-    const float px0 = visible ? (float)(ex - oxd) : 0.f, py0 = visible ? (float)(ey - oyd) : 0.f,
-                pz0 = visible ? (float)(ez - ozd) : 0.f;
-    const float lox = -5.5f - (float)ox, loy = -1.5f - (float)oy, loz = -5.5f - (float)oz;   // build-zone box
-    const float ground = -1.5f - (float)oy;
-    __syncthreads();
-    const uint32_t* s_occ = reinterpret_cast<const uint32_t*>(s_occ4);
-    const int8_t* s_grid = reinterpret_cast<const int8_t*>(s_grid4);
-    uint8_t* stage = reinterpret_cast<uint8_t*>(s_stage4);
+    render_frame(pose, reinterpret_cast<const uint32_t*>(s_occ4), reinterpret_cast<const int8_t*>(s_grid4), s_stage4,
+                 atlas, side, out, env, W, H, C);
+}
 
-    const int wh = W * H;
-    const int c0 = blockIdx.y * kChunk;
-    const int len = min(kChunk, wh - c0);
-    const int sub = side >> 3;                // texels of a half tile (tex_coord(..., split=True))
-    const float inv_h = 1.f / (float)H;
-    for (int q = tid; q < len; q += kThreads) {
-        const int pix = c0 + q;
-        const int i = pix / W, j = pix - (pix / W) * W;
-        uint32_t rgba = IGW_RENDER_CLEAR_RGBA;
-        if (visible) {
-            // d = f + ((2j+1)/W - 1)(W/H) r + (1 - (2i+1)/H) u: t along d is the eye-space depth
-            const float a = (float)(2 * j + 1 - W) * inv_h, b = (float)(H - 2 * i - 1) * inv_h;
-            const float dx = fx + a * rx + b * ux, dy = fy + b * uy, dz = fz + a * rz + b * uz;
-            const float ix = 1.f / dx, iy = 1.f / dy, iz = 1.f / dz;
-            // clip to the box [lo, lo + n]
-            float t0 = 0.f, t1 = kFar;
-            int axis = -1;
-            bool miss = false;
-#define IGW_SLAB(P, D, I, LO, N, K)                                                       \
-            if (D != 0.f) {                                                               \
-                float ta = (LO - P) * I, tb = (LO + N - P) * I;                           \
-                if (ta > tb) { float s = ta; ta = tb; tb = s; }                           \
-                if (ta > t0) { t0 = ta; axis = K; }                                       \
-                t1 = fminf(t1, tb);                                                       \
-            } else if (P < LO || P > LO + N) miss = true;
-            IGW_SLAB(px0, dx, ix, lox, 11.f, 0)
-            IGW_SLAB(py0, dy, iy, loy, 9.f, 1)
-            IGW_SLAB(pz0, dz, iz, loz, 11.f, 2)
-#undef IGW_SLAB
-            int face = -1, hx = 0, hy = 0, hz = 0;
-            float th = 0.f;
-            if (!miss && t0 <= t1) {
-                int cx = min(max((int)floorf(px0 + t0 * dx - lox), 0), 10);
-                int cyy = min(max((int)floorf(py0 + t0 * dy - loy), 0), 8);
-                int cz = min(max((int)floorf(pz0 + t0 * dz - loz), 0), 10);
-                if (axis == 0) cx = dx > 0.f ? 0 : 10;
-                if (axis == 1) cyy = dy > 0.f ? 0 : 8;
-                if (axis == 2) cz = dz > 0.f ? 0 : 10;
-                const int face_x = dx > 0.f ? kLeft : kRight, face_y = dy > 0.f ? kBottom : kTop,
-                          face_z = dz > 0.f ? kBack : kFront;
-                if (axis >= 0 && t0 >= kNear && occupied(s_occ, cyy, cx, cz)) {
-                    face = axis == 0 ? face_x : axis == 1 ? face_y : face_z;
-                    th = t0;
-                }
-                const int sx = dx > 0.f ? 1 : -1, syy = dy > 0.f ? 1 : -1, sz = dz > 0.f ? 1 : -1;
-                // the next boundary crossed on each axis, recomputed from the cell (no accumulated error)
-                float nx = dx != 0.f ? (lox + (float)(cx + (dx > 0.f)) - px0) * ix : INFINITY;
-                float ny = dy != 0.f ? (loy + (float)(cyy + (dy > 0.f)) - py0) * iy : INFINITY;
-                float nz = dz != 0.f ? (loz + (float)(cz + (dz > 0.f)) - pz0) * iz : INFINITY;
-                // at most 10 + 8 + 10 crossings inside the box
-                for (int it = 0; face < 0 && it < 30; ++it) {
-                    float t;
-                    int f;
-                    if (nx <= ny && nx <= nz) {
-                        t = nx; cx += sx; f = face_x;
-                        if (cx < 0 || cx > 10) break;
-                        nx = (lox + (float)(cx + (dx > 0.f)) - px0) * ix;
-                    } else if (ny <= nz) {
-                        t = ny; cyy += syy; f = face_y;
-                        if (cyy < 0 || cyy > 8) break;
-                        ny = (loy + (float)(cyy + (dy > 0.f)) - py0) * iy;
-                    } else {
-                        t = nz; cz += sz; f = face_z;
-                        if (cz < 0 || cz > 10) break;
-                        nz = (loz + (float)(cz + (dz > 0.f)) - pz0) * iz;
-                    }
-                    if (t > kFar) break;
-                    if (t >= kNear && occupied(s_occ, cyy, cx, cz)) { face = f; th = t; }
-                }
-                hx = cx; hy = cyy; hz = cz;
-            }
-            int col = -1, rowb = 0;
-            if (face >= 0) {
-                // where the ray enters the cell, in the cell's own unit coordinates
-                const float lx = px0 + th * dx - (lox + (float)hx), ly = py0 + th * dy - (loy + (float)hy),
-                            lz = pz0 + th * dz - (loz + (float)hz);
-                // u / v of each face: vertex order of cube_vertices against corner order of tex_coord
-                // (gridworld/utils.py:26-43, 82-123); sub-tile (cx, cy) per face: top (0, 1/8), bottom (1/8, 0),
-                // left / right (0, 0), front / back (1/8, 1/8)
-                float u, v;
-                int cu, cv;
-                switch (face) {
-                    case kTop: u = lz; v = lx; cu = 0; cv = 1; break;
-                    case kBottom: u = lx; v = lz; cu = 1; cv = 0; break;
-                    case kLeft: u = lz; v = ly; cu = 0; cv = 0; break;
-                    case kRight: u = 1.f - lz; v = ly; cu = 0; cv = 0; break;
-                    case kFront: u = lx; v = ly; cu = 1; cv = 1; break;
-                    default: u = 1.f - lx; v = ly; cu = 1; cv = 1; break;
-                }
-                int id = s_grid[hy * 121 + hx * 11 + hz];
-                id = id < 1 ? 1 : id > 6 ? 6 : id;   // BLUE .. YELLOW (world grids hold no other id)
-                const int tile = id + 1;            // tiles (2,0) (3,0) (0,1) (1,1) (2,1) (3,1), utils.py:139-146
-                col = (tile & 3) * 2 * sub + cu * sub + texel_index(u, sub);
-                rowb = (tile >> 2) * 2 * sub + cv * sub + texel_index(v, sub);
-            } else if (dy < 0.f && py0 > ground) {
-                // the ground: top faces of the 37 x 37 quads centred on x, z in [-18, 18] at y = -1.5 (world.py:60-71)
-                const float t = (ground - py0) * iy;
-                if (t >= kNear && t <= kFar) {
-                    const float gx = px0 + t * dx + 0.5f, gz = pz0 + t * dz + 0.5f;
-                    const float fgx = floorf(gx), fgz = floorf(gz);
-                    const int qx = ox + (int)fgx, qz = oz + (int)fgz;   // centre of the quad hit
-                    if (qx >= -18 && qx <= 18 && qz >= -18 && qz <= 18) {
-                        const int tile = (qx >= -5 && qx <= 5 && qz >= -5 && qz <= 5) ? 0 : 1;   // WHITE : GREY
-                        col = tile * 2 * sub + texel_index(gz - fgz, 2 * sub);   // top face: u = z, v = x
-                        rowb = texel_index(gx - fgx, 2 * sub);
-                    }
-                }
-            }
-            if (col >= 0) rgba = atlas[(side - 1 - rowb) * side + col];   // v = 0 is the bottom image row
-        }
-        if (C == 4) {
-            reinterpret_cast<uint32_t*>(stage)[q] = rgba;
-        } else {
-            stage[3 * q] = (uint8_t)rgba;
-            stage[3 * q + 1] = (uint8_t)(rgba >> 8);
-            stage[3 * q + 2] = (uint8_t)(rgba >> 16);
-        }
+// Block (episode e, entry t, chunk): frame t of episode e, rebuilt from the episode log (igw_render.h:
+// igw_render_episodes).  The grid is the start grid with the last change of every cell among records 0..t-1 applied:
+// one strided pass over the records keeps, per cell, max(record << 3 | colour) in an LDS table (the staging area,
+// free until the pixels are shaded); the occupancy bitmap is then derived from the grid.
+__global__ __launch_bounds__(kThreads) void igw_render_episodes_kernel(
+    const uint8_t* __restrict__ records, int64_t n_records, const int64_t* __restrict__ first,
+    const int32_t* __restrict__ length, const int64_t* __restrict__ frame0, const int8_t* __restrict__ start_grid,
+    const double* __restrict__ init_pose, int max_length, const uint32_t* __restrict__ atlas, int side,
+    uint8_t* __restrict__ out, int64_t n_frames, int W, int H, int C) {
+    __shared__ uint4 s_grid4[kGridStride / 16];
+    __shared__ uint4 s_occ4[kOccWords / 4];
+    __shared__ uint4 s_stage4[kChunk * 4 / 16];
+    const int tid = threadIdx.x;
+    const int64_t e = blockIdx.x / (unsigned)(max_length + 1);
+    const int t = (int)(blockIdx.x - e * (max_length + 1));
+    // device-side values are not trusted: the length is clamped, an episode outside the buffers is not drawn
+    const int len = min(max(length[e], 0), max_length);
+    const int64_t r0 = first[e], f0 = frame0[e];
+    if (t > len || r0 < 0 || r0 > n_records - len || f0 < 0 || f0 > n_frames - (len + 1)) return;
+
+    int* s_last = reinterpret_cast<int*>(s_stage4);
+    int8_t* s_grid = reinterpret_cast<int8_t*>(s_grid4);
+    uint32_t* s_occ = reinterpret_cast<uint32_t*>(s_occ4);
+    if (tid < kGridStride / 16) s_grid4[tid] = reinterpret_cast<const uint4*>(start_grid + e * kGridStride)[tid];
+    for (int c = tid; c < kCells; c += kThreads) s_last[c] = -1;
+    // entry 0: the reset pose (f64, task_meta order x, y, z, yaw, pitch); entry t: the f32 agentPos of record t-1
+    // (x, y, z, pitch, yaw) widened to f64
+    double pose[5];
+    if (t == 0) {
+        for (int k = 0; k < 5; k++) pose[k] = init_pose[5 * e + k];
+    } else {
+        const float* p = reinterpret_cast<const float*>(records + (r0 + t - 1) * kTrajBytes);
+        pose[0] = p[0]; pose[1] = p[1]; pose[2] = p[2]; pose[3] = p[4]; pose[4] = p[3];
     }
     __syncthreads();
-    // the chunk's bytes are contiguous in the frame: 16-byte stores where the alignment allows
-    const int nbytes = len * C;
-    uint8_t* dst = out + (env * (int64_t)wh + c0) * C;
-    if (((reinterpret_cast<uintptr_t>(dst) | (uintptr_t)nbytes) & 15) == 0) {
-        for (int k = tid; k < nbytes / 16; k += kThreads) reinterpret_cast<uint4*>(dst)[k] = s_stage4[k];
-    } else if (((reinterpret_cast<uintptr_t>(dst) | (uintptr_t)nbytes) & 3) == 0) {
-        for (int k = tid; k < nbytes / 4; k += kThreads)
-            reinterpret_cast<uint32_t*>(dst)[k] = reinterpret_cast<const uint32_t*>(stage)[k];
-    } else {
-        for (int k = tid; k < nbytes; k += kThreads) dst[k] = stage[k];
+    const uint8_t* rec = records + r0 * kTrajBytes;
+    for (int k = tid; k < t; k += kThreads) {
+        const uint32_t ch = *reinterpret_cast<const uint16_t*>(rec + (int64_t)k * kTrajBytes + 40);
+        const uint32_t cell = ch & 0x7ffu;
+        if (ch != 0xffffu && cell < (uint32_t)kCells) atomicMax(&s_last[cell], (k << 3) | (int)((ch >> 11) & 7u));
     }
+    __syncthreads();
+    for (int c = tid; c < kCells; c += kThreads) {
+        const int w = s_last[c];
+        if (w >= 0) s_grid[c] = (int8_t)(w & 7);
+    }
+    __syncthreads();
+    if (tid < kOccWords) {   // include/igw.h: bit (y+1)*169 + (x+6)*13 + (z+6) of grid[y+1][x+5][z+5]
+        uint32_t bits = 0;
+        for (int b = 0; b < 32; b++) {
+            const int i = tid * 32 + b, yv = i / 169, r = i - yv * 169, xp = r / 13, zp = r - xp * 13;
+            if (yv < 9 && xp >= 1 && xp <= 11 && zp >= 1 && zp <= 11 && s_grid[yv * 121 + (xp - 1) * 11 + (zp - 1)] != 0)
+                bits |= 1u << b;
+        }
+        s_occ[tid] = bits;
+    }
+    render_frame(pose, s_occ, s_grid, s_stage4, atlas, side, out, f0 + t, W, H, C);
 }
 
 thread_local char g_err[512] = "";
@@ -217,6 +104,16 @@ int fail(int code, const char* fmt, const char* detail = "") {
 }
 
 bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
+bool have_device() {
+    static int seen = 0;   // once a device was seen it stays (the count is not re-queried per frame)
+    if (!seen) {
+        int cnt = 0;
+        if (hipGetDeviceCount(&cnt) != hipSuccess || cnt < 1) return false;
+        seen = 1;
+    }
+    return true;
+}
 
 }  // namespace
 
@@ -244,14 +141,8 @@ int igw_render_pov(const void* agent, const int8_t* grid, const uint32_t* occ, i
     if (!aligned(agent, 8) || !aligned(grid, 16) || !aligned(occ, 16) || !aligned(atlas, 4))
         return fail(IGW_RENDER_ERR_INVALID, "igw_render_pov: agent must be 8-byte, grid and occ 16-byte, atlas "
                                             "4-byte aligned");
-    static int have_device = 0;   // once a device was seen it stays (the count is not re-queried per frame)
-    if (!have_device) {
-        int cnt = 0;
-        if (hipGetDeviceCount(&cnt) != hipSuccess || cnt < 1)
-            return fail(IGW_RENDER_ERR_NO_DEVICE,
-                        "igw_render_pov: no HIP device available (the renderer has no CPU fallback)");
-        have_device = 1;
-    }
+    if (!have_device())
+        return fail(IGW_RENDER_ERR_NO_DEVICE, "igw_render_pov: no HIP device available (the renderer has no CPU fallback)");
     if (n == 0) return IGW_RENDER_OK;
     const int chunks = (width * height + kChunk - 1) / kChunk;
     hipLaunchKernelGGL(igw_render_pov_kernel, dim3((unsigned)n, (unsigned)chunks), dim3(kThreads), 0,
@@ -260,6 +151,42 @@ int igw_render_pov(const void* agent, const int8_t* grid, const uint32_t* occ, i
                        (int)channels);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(IGW_RENDER_ERR_HIP, "igw_render_pov: launch failed: %s", hipGetErrorString(e));
+    return IGW_RENDER_OK;
+}
+
+int igw_render_episodes(const uint8_t* records, int64_t n_records, const int64_t* first, const int32_t* length,
+                        const int64_t* frame0, const int8_t* start_grid, const double* init_pose, int32_t m,
+                        int32_t max_length, const uint8_t* atlas, int32_t atlas_side, uint8_t* out, int64_t n_frames,
+                        int32_t width, int32_t height, int32_t channels, void* stream) {
+    if (m < 0) return fail(IGW_RENDER_ERR_INVALID, "igw_render_episodes: m must be >= 0");
+    if (max_length < 0 || max_length > IGW_RENDER_MAX_EPISODE)
+        return fail(IGW_RENDER_ERR_INVALID, "igw_render_episodes: max_length must be in 0..2^24");
+    if ((int64_t)m * (max_length + 1) > INT32_MAX)
+        return fail(IGW_RENDER_ERR_INVALID, "igw_render_episodes: m * (max_length + 1) must be < 2^31");
+    if (n_records < 0 || n_frames < 0)
+        return fail(IGW_RENDER_ERR_INVALID, "igw_render_episodes: n_records and n_frames must be >= 0");
+    if (channels != 3 && channels != 4)
+        return fail(IGW_RENDER_ERR_INVALID, "igw_render_episodes: channels must be 3 or 4");
+    if (width < 1 || width > IGW_RENDER_MAX_SIDE || height < 1 || height > IGW_RENDER_MAX_SIDE)
+        return fail(IGW_RENDER_ERR_INVALID, "igw_render_episodes: width and height must be in 1..1024");
+    if (atlas_side < 8 || atlas_side > IGW_RENDER_MAX_ATLAS || atlas_side % 8)
+        return fail(IGW_RENDER_ERR_INVALID, "igw_render_episodes: atlas_side must be a multiple of 8 in 8..256");
+    if (m > 0 && (!records || !first || !length || !frame0 || !start_grid || !init_pose || !atlas || !out))
+        return fail(IGW_RENDER_ERR_INVALID, "igw_render_episodes: null buffer");
+    if (!aligned(records, 16) || !aligned(first, 8) || !aligned(length, 4) || !aligned(frame0, 8) ||
+        !aligned(start_grid, 16) || !aligned(init_pose, 8) || !aligned(atlas, 4))
+        return fail(IGW_RENDER_ERR_INVALID, "igw_render_episodes: records and start_grid must be 16-byte, first, "
+                                            "frame0 and init_pose 8-byte, length and atlas 4-byte aligned");
+    if (!have_device()) return fail(IGW_RENDER_ERR_NO_DEVICE, "igw_render_episodes: no HIP device available (the renderer has no CPU fallback)");
+    if (m == 0) return IGW_RENDER_OK;
+    const int chunks = (width * height + kChunk - 1) / kChunk;
+    hipLaunchKernelGGL(igw_render_episodes_kernel, dim3((unsigned)(m * (max_length + 1)), (unsigned)chunks),
+                       dim3(kThreads), 0, (hipStream_t)stream, records, n_records, first, length, frame0, start_grid,
+                       init_pose, (int)max_length, reinterpret_cast<const uint32_t*>(atlas), (int)atlas_side, out,
+                       n_frames, (int)width, (int)height, (int)channels);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess)
+        return fail(IGW_RENDER_ERR_HIP, "igw_render_episodes: launch failed: %s", hipGetErrorString(e));
     return IGW_RENDER_OK;
 }
 

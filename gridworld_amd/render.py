@@ -22,12 +22,14 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc', 'render')
 LIB = os.path.join(HERE, 'libigw_render.so')
 SOURCES = [os.path.join(CSRC, 'igw_render.hip')]
-HEADERS = [os.path.join(HERE, '..', 'include', 'igw_render.h')]
+HEADERS = [os.path.join(CSRC, 'igw_render_frame.h'), os.path.join(HERE, '..', 'include', 'igw_render.h')]
 VERSION = 1
 MAX_SIDE = 1024
 MAX_ATLAS = 256
+MAX_EPISODE = 1 << 24
 CLEAR_RGBA = (128, 176, 255, 255)   # unorm8 of glClearColor(0.5, 0.69, 1.0, 1), gridworld/render.py:41
-EXPORTS = ['igw_render_version', 'igw_render_build_id', 'igw_render_last_error', 'igw_render_pov']
+EXPORTS = ['igw_render_version', 'igw_render_build_id', 'igw_render_last_error', 'igw_render_pov',
+           'igw_render_episodes']
 _MARK = b'igw-render-build-id:'
 
 
@@ -114,6 +116,9 @@ def load(build_if_missing=True):
     L.igw_render_last_error.restype = C.c_char_p
     L.igw_render_pov.argtypes = [vp, vp, vp, i32, vp, i32, vp, i32, i32, i32, vp]
     L.igw_render_pov.restype = C.c_int
+    i64 = C.c_int64
+    L.igw_render_episodes.argtypes = [vp, i64, vp, vp, vp, vp, vp, i32, i32, vp, i32, vp, i64, i32, i32, i32, vp]
+    L.igw_render_episodes.restype = C.c_int
     _lib = L
     return L
 
@@ -178,6 +183,17 @@ def render_into(agent, grid, occ, n, atlas, out, width, height, channels, stream
                           int(height), int(channels), stream)
     if rc:
         check(rc)
+
+
+def render_episodes_into(records, n_records, first, length, frame0, start_grid, init_pose, m, max_length, atlas, out,
+                         n_frames, width, height, channels, stream):
+    """One igw_render_episodes call on raw pointers (ints); `atlas` is a device tensor [S, S, 4]."""
+    L = load()
+    rc = L.igw_render_episodes(records, int(n_records), first, length, frame0, start_grid, init_pose, int(m),
+                               int(max_length), atlas.data_ptr(), int(atlas.shape[0]), out, int(n_frames), int(width),
+                               int(height), int(channels), stream)
+    if rc:
+        check(rc, 'igw_render_episodes')
 
 
 if __name__ == '__main__':

@@ -33,12 +33,21 @@ class EpisodeLogger:
     device record packs a flying action's inventory into 3 bits and its placement into 2 (include/igw.h), so an
     inventory id the kernel rejected (outside 0..6: run as 0 and counted in stats()['bad_actions']) is logged as 0 and
     a placement other than 1 / 2 as 0.  Replaying a log therefore reproduces the trajectory, not the bad-action
-    counts; Discrete(18) ids, movement / camera floats and Dict buttons are logged raw."""
+    counts; Discrete(18) ids, movement / camera floats and Dict buttons are logged raw.
 
-    def __init__(self, vec, n_envs=1, path='episodes', desc='', glob_step=0, capacity=None):
+    pov=True adds `pov` uint8 [T+1, H, W, 3] (W, H = vec.render_size, RGB, the env's atlas): the first-person frame of
+    every entry, drawn on the device by ONE igw_render_episodes launch per collect() for all the episodes it returns
+    (include/igw_render.h).  Entry 0 is the reset state seen from the task row's f64 init pose; entry t >= 1 is grid[t]
+    seen from agentPos[t], the f32 pose the log holds ("First-person frames").  The last entry of an
+    episode that ended in an auto-reset is its terminal state, which render_pov() can no longer show.  Like `grid`,
+    the frames read the episode's task row (starting grid, init pose): a set_tasks that rewrites that row between the
+    episode and collect() changes them."""
+
+    def __init__(self, vec, n_envs=1, path='episodes', desc='', glob_step=0, capacity=None, pov=False):
         import numpy as np
         self.np = np
         self.vec, self.path, self.desc, self.glob_step = vec, path, desc, glob_step
+        self.pov = bool(pov)
         self.records, self.heads = vec.enable_trajectory_log(n_envs, capacity)
         self.n_envs = int(n_envs)
         self._dumped = {}  # env -> last episode number written
@@ -83,6 +92,33 @@ class EpisodeLogger:
                 'grid': grids, 'reward': f32[:, 5].astype(np.float64), 'done': raw[:, 42].astype(bool),
                 'actions': actions, 'task': int(task)}
 
+    def _render(self, todo):
+        """pov frames of the episodes (env, slot, task, length, episode) in one igw_render_episodes launch on the env's
+        stream: a list of uint8 [length + 1, H, W, 3] arrays."""
+        np = self.np
+        import torch
+        from . import render as R
+        v = self.vec
+        if not todo:
+            return []
+        dev, cap = v.device, self.records.shape[2]
+        env, slot, task, length = (np.array([t[i] for t in todo], np.int64) for i in range(4))
+        frame0 = np.concatenate([[0], np.cumsum(length + 1)])
+        rows = torch.from_numpy(task).to(dev)
+        first = torch.from_numpy((env * 2 + slot) * cap).to(dev)
+        length_d = torch.from_numpy(length.astype(np.int32)).to(dev)
+        frame0_d = torch.from_numpy(frame0[:-1].copy()).to(dev)
+        start = v.task_start.index_select(0, rows)                                     # [m, 1104] i8
+        pose = v.task_meta.index_select(0, rows)[:, :40].contiguous().view(torch.float64)   # [m, 5] x, y, z, yaw, pitch
+        W, H = v.render_size
+        n_frames = int(frame0[-1])
+        out = torch.empty((n_frames, H, W, 3), dtype=torch.uint8, device=dev)
+        R.render_episodes_into(self.records.data_ptr(), self.records.shape[0] * 2 * cap, first.data_ptr(),
+                               length_d.data_ptr(), frame0_d.data_ptr(), start.data_ptr(), pose.data_ptr(), len(todo),
+                               cap, v._atlas(), out.data_ptr(), n_frames, W, H, 3, v._stream())
+        host = out.cpu().numpy()
+        return [host[frame0[k]:frame0[k + 1]] for k in range(len(todo))]
+
     def collect(self, dump=True):
         """Decodes (and with dump=True writes) every logged episode that finished since the last call."""
         import os
@@ -91,42 +127,53 @@ class EpisodeLogger:
         import torch
         torch.cuda.synchronize(self.vec.device)
         heads = self.heads.cpu().numpy()
-        out = []
+        todo = []
         for env in range(self.n_envs):
             for slot in (0, 1):
                 task, length, episode, finished = (int(x) for x in heads[env, slot])
                 if not finished or length == 0 or self._dumped.get(env, -1) >= episode:
                     continue
-                ep = self._decode(env, slot, task, length)
-                ep.update(env=env, episode=episode)
+                todo.append((env, slot, task, length, episode))
                 self._dumped[env] = max(self._dumped.get(env, -1), episode)
-                if dump:
-                    d = f'{self.path}/step{self.glob_step}'
-                    os.makedirs(d, exist_ok=True)
-                    fname = f'{d}/ep_{self.desc}_{uuid.uuid4().hex[:6]}'
-                    arrays = {k: v for k, v in ep.items() if k != 'actions'}
-                    if isinstance(ep['actions'], dict):
-                        arrays.update({'action_' + k: v for k, v in ep['actions'].items()})
-                    np.savez_compressed(fname + '.npz', **arrays)
-                    if not isinstance(ep['actions'], dict):
-                        with open(fname + '.csv', 'w') as f:
-                            for a in ep['actions']:
-                                f.write(f'{int(a)}\n')
-                    ep['file'] = fname + '.npz'
-                out.append(ep)
+        frames = self._render(todo) if self.pov else None
+        out = []
+        for i, (env, slot, task, length, episode) in enumerate(todo):
+            ep = self._decode(env, slot, task, length)
+            ep.update(env=env, episode=episode)
+            if frames is not None:
+                ep['pov'] = frames[i]
+            if dump:
+                d = f'{self.path}/step{self.glob_step}'
+                os.makedirs(d, exist_ok=True)
+                fname = f'{d}/ep_{self.desc}_{uuid.uuid4().hex[:6]}'
+                arrays = {k: v for k, v in ep.items() if k != 'actions'}
+                if isinstance(ep['actions'], dict):
+                    arrays.update({'action_' + k: v for k, v in ep['actions'].items()})
+                np.savez_compressed(fname + '.npz', **arrays)
+                if not isinstance(ep['actions'], dict):
+                    with open(fname + '.csv', 'w') as f:
+                        for a in ep['actions']:
+                            f.write(f'{int(a)}\n')
+                ep['file'] = fname + '.npz'
+            out.append(ep)
         self.episodes.extend(out)
         return out
 
 
 class Logged(Wrapper):
-    """The reference's Logged wrapper for the 1-env facade (gridworld/wrappers.py:66-134), without the renderer:
-    turn_on() / set_path() / set_desc(); an episode is written when it ends while logging is on."""
+    """The reference's Logged wrapper for the 1-env facade (gridworld/wrappers.py:66-134): turn_on() / set_path() /
+    set_desc(); an episode is written when it ends while logging is on.  When the env draws frames (render=True,
+    renderer='hip', not fake) the npz holds `pov` uint8 [T+1, H, W, 3], one RGB frame per entry, equal to the env's
+    obs['pov'] after each step (up to f32 rounding of the logged pose, EpisodeLogger).  The reference's own list
+    interleaves that RGB frame with a render() frame flipped to BGR for its cv2 video writer (wrappers.py:95-100);
+    here there is one RGB frame per entry and no video."""
 
     def __init__(self, env):
         super().__init__(env)
         self.logging = False
         self.turned_off = True
-        self._log = EpisodeLogger(env.unwrapped._vec, 1, path='episodes')
+        u = env.unwrapped
+        self._log = EpisodeLogger(u._vec, 1, path='episodes', pov=u._renders())
 
     def turn_on(self):
         self.turned_off = False

@@ -28,6 +28,7 @@ extern "C" {
 #define IGW_RENDER_MAX_SIDE 1024      /* largest frame width / height */
 #define IGW_RENDER_MAX_ATLAS 256      /* largest atlas side (texels); the side is a multiple of 8 */
 #define IGW_RENDER_CLEAR_RGBA 0xFFFFB080u  /* (128, 176, 255, 255) as little-endian RGBA bytes */
+#define IGW_RENDER_MAX_EPISODE (1 << 24)  /* largest max_length of igw_render_episodes */
 
 enum igw_render_status {
     IGW_RENDER_OK = 0,
@@ -52,6 +53,32 @@ const char* igw_render_last_error(void);
  */
 int igw_render_pov(const void* agent, const int8_t* grid, const uint32_t* occ, int32_t n, const uint8_t* atlas,
                    int32_t atlas_side, uint8_t* out, int32_t width, int32_t height, int32_t channels, void* stream);
+
+/*
+ * Renders every entry of m logged episodes from the episode log of the step path (include/igw.h:
+ * igw_set_trajectory_log), in one launch.  Episode e has length[e] + 1 frames, written to out[frame0[e] + t]
+ * ([n_frames][height][width][channels] uint8) for t = 0 .. length[e]:
+ *   t = 0   the reset state: start_grid[e] seen from init_pose[e] (f64);
+ *   t >= 1  the state after step t: start_grid[e] with the `change` of records[first[e]] .. records[first[e] + t - 1]
+ *           applied in order, seen from the f32 agentPos of records[first[e] + t - 1] widened to f64 (agentPos is
+ *           x, y, z, pitch, yaw: the angles are swapped against init_pose).
+ * Frame t is bit-identical to what igw_render_pov draws for an agent record holding that pose and that grid.
+ *   records    [n_records][IGW_TRAJ_BYTES] the log (16-byte aligned); an episode's records are consecutive
+ *   first      [m] i64  index in records of the episode's first record
+ *   length     [m] i32  steps recorded; clamped to 0 .. max_length on the device
+ *   frame0     [m] i64  index in out of the episode's entry 0
+ *   start_grid [m][1104] i8 grid the reset wrote (the task row's starting grid, include/igw.h: task_start)
+ *   init_pose  [m][5] f64  x, y, z, yaw, pitch of the reset (task_meta bytes 0..39)
+ * Every array is a device array and is read on the device only: the call never reads it on the host, never
+ * allocates, never synchronises.  Device-side values are not trusted: a change to a cell >= 1089 is ignored, and an
+ * episode whose records [first, first + length) or frames [frame0, frame0 + length] fall outside n_records / n_frames
+ * is not drawn.  Frames of entries past length[e] are not written.  0 <= max_length <= IGW_RENDER_MAX_EPISODE and
+ * m * (max_length + 1) < 2^31; atlas, size and channels as for igw_render_pov.  m == 0 is a no-op.
+ */
+int igw_render_episodes(const uint8_t* records, int64_t n_records, const int64_t* first, const int32_t* length,
+                        const int64_t* frame0, const int8_t* start_grid, const double* init_pose, int32_t m,
+                        int32_t max_length, const uint8_t* atlas, int32_t atlas_side, uint8_t* out, int64_t n_frames,
+                        int32_t width, int32_t height, int32_t channels, void* stream);
 
 #ifdef __cplusplus
 }

@@ -9,6 +9,15 @@
 
     python tools/bench_render.py [--envs 1,4096,65536,524288] [--iters 50] [--out profiles/r07_render_bench.json]
 
+--mode episodes measures the log frames (igw_render_episodes) instead, on episodes of --steps walking steps logged
+for --episodes envs (default 4,096 x 250: 1.03 M frames of 64 x 64 RGB):
+
+  episodes  one igw_render_episodes launch over all of them: us per launch, frames / s
+  logged64  the frames of 64 logged envs two ways: igw_render_pov of the 64 rows after every step (--steps launches,
+            summed) against one igw_render_episodes launch for the 64 finished episodes
+
+    python tools/bench_render.py --mode episodes [--out profiles/r08_render_episodes_bench.json]
+
 The VALU side of the kernel comes from a separate profiler run ("First-person frames": measured numbers).
 """
 import argparse
@@ -101,6 +110,69 @@ def bench_facade(steps):
     return res
 
 
+def _logged_episodes(n, steps):
+    """n walking envs stepped `steps` times with the whole batch logged (max_steps = steps, so every env finishes one
+    episode at the last step): (env, records, device arrays first / length / frame0 / start / pose of the finished
+    episodes, frames)."""
+    from gridworld_amd import VecGridWorld, workloads
+    env = VecGridWorld(n, max_steps=steps, autoreset=True)
+    rng = np.random.RandomState(2)
+    pose = np.stack([rng.uniform(-8, 8, n), rng.uniform(0, 4, n), rng.uniform(-8, 8, n), rng.uniform(-180, 180, n),
+                     rng.uniform(-60, 60, n)], 1)
+    env.set_tasks(workloads.rt20(n, seed=2).numpy(), workloads.uniform20(n, seed=2).numpy(), init_pose=pose)
+    rec, heads = env.enable_trajectory_log(n, steps)
+    env.reset()
+    acts = env.fill_actions(steps, seed=5)
+    for t in range(steps):
+        env.step_walking_ptr(acts[t])
+    torch.cuda.synchronize()
+    h = heads.cpu().numpy()
+    slot = np.argmax(h[:, :, 3], axis=1)                  # the slot whose episode finished
+    assert (h[np.arange(n), slot, 3] == 1).all() and (h[np.arange(n), slot, 1] == steps).all()
+    task = h[np.arange(n), slot, 0].astype(np.int64)
+    dev = env.device
+    rows = torch.from_numpy(task).to(dev)
+    arrays = dict(first=torch.from_numpy((np.arange(n) * 2 + slot) * steps).to(dev),
+                  length=torch.full((n,), steps, dtype=torch.int32, device=dev),
+                  frame0=torch.arange(n, dtype=torch.int64, device=dev) * (steps + 1),
+                  start=env.task_start.index_select(0, rows),
+                  pose=env.task_meta.index_select(0, rows)[:, :40].contiguous().view(torch.float64))
+    return env, rec, arrays
+
+
+def _episodes_call(env, rec, a, m, steps, out):
+    from gridworld_amd import render as R
+    stream = torch.cuda.current_stream().cuda_stream
+    return lambda: R.render_episodes_into(rec.data_ptr(), rec.shape[0] * 2 * steps, a['first'].data_ptr(),
+                                          a['length'].data_ptr(), a['frame0'].data_ptr(), a['start'].data_ptr(),
+                                          a['pose'].data_ptr(), m, steps, env._atlas(), out.data_ptr(), out.shape[0],
+                                          64, 64, 3, stream)
+
+
+def bench_episodes(n, steps, iters, warmup):
+    env, rec, a = _logged_episodes(n, steps)
+    frames = n * (steps + 1)
+    out = torch.empty((frames, 64, 64, 3), dtype=torch.uint8, device='cuda')
+    us = _time(_episodes_call(env, rec, a, n, steps, out), iters, warmup)
+    res = {'episodes': n, 'steps': steps, 'frames': frames, 'size': [64, 64], 'channels': 3,
+           'us_per_launch': round(us, 1), 'frames_per_s': round(frames / (us * 1e-6), 1)}
+    # 64 logged envs: one launch for their episodes, against igw_render_pov of the same 64 rows after every step
+    out64 = torch.empty((64 * (steps + 1), 64, 64, 3), dtype=torch.uint8, device='cuda')
+    one = _time(_episodes_call(env, rec, a, 64, steps, out64), iters, warmup)
+    live = torch.empty((64, 64, 64, 3), dtype=torch.uint8, device='cuda')
+    from gridworld_amd import render as R
+    stream = torch.cuda.current_stream().cuda_stream
+    rows64 = (env.agent_buf.data_ptr(), env.grid_buf.data_ptr(), env.occ_buf.data_ptr(), 64)
+    per_step = _time(lambda: R.render_into(*rows64, env._atlas(), live.data_ptr(), 64, 64, 3, stream), iters * 5,
+                     warmup)
+    res['logged64'] = {'episodes': 64, 'frames': 64 * (steps + 1),
+                       'render_pov_us_per_launch': round(per_step, 2),
+                       'render_pov_every_step_us': round(per_step * steps, 1),
+                       'render_episodes_one_launch_us': round(one, 1),
+                       'speedup': round(per_step * steps / one, 2)}
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--envs', default='1,4096,65536,524288')
@@ -109,13 +181,20 @@ def main():
     ap.add_argument('--facade-steps', type=int, default=500)
     ap.add_argument('--skip', default='', help='comma list of parts to skip: step, facade')
     ap.add_argument('--out', default=None)
+    ap.add_argument('--mode', default='render', choices=('render', 'episodes'))
+    ap.add_argument('--episodes', type=int, default=4096)
+    ap.add_argument('--steps', type=int, default=250)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit('bench_render.py needs a GPU')
     from gridworld_amd import render as R, build as B
     skip = set(filter(None, a.skip.split(',')))
     line = {'tool': 'tools/bench_render.py', 'render_build_id': R.build_id(), 'step_build_id': B.source_hash(),
-            'device': torch.cuda.get_device_name(0), 'render': []}
+            'device': torch.cuda.get_device_name(0)}
+    if a.mode == 'episodes':
+        line['episodes'] = bench_episodes(a.episodes, a.steps, a.iters, a.warmup)
+        return _emit(line, a.out)
+    line['render'] = []
     for n in [int(v) for v in a.envs.split(',')]:
         try:
             line['render'].append(bench_render(n, a.iters, a.warmup))
@@ -125,11 +204,15 @@ def main():
         line['step'] = bench_step(65536, a.iters, a.warmup)
     if 'facade' not in skip:
         line['facade'] = bench_facade(a.facade_steps)
+    _emit(line, a.out)
+
+
+def _emit(line, out):
     s = json.dumps(line)
     print(s)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, 'w') as f:
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, 'w') as f:
             f.write(s + '\n')
 
 
