@@ -10,3 +10,5 @@ __version__ = '0.1.0'
 from .env import GridWorld, SizeReward, Wrapper, create_env, make, make_vec, register  # noqa: F401,E402
 from .tasks import Task, Tasks, CustomTasks, RandomTasks, Subtasks, dummy_task  # noqa: F401,E402
 from . import workloads  # noqa: F401,E402
+from . import visualizer  # noqa: F401,E402
+from .visualizer import Visualizer, look_at, orbit_poses, render_views  # noqa: F401,E402

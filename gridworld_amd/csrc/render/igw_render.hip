@@ -96,6 +96,48 @@ __global__ __launch_bounds__(kThreads) void igw_render_episodes_kernel(
     render_frame(pose, s_occ, s_grid, s_stage4, atlas, side, out, f0 + t, W, H, C);
 }
 
+// Block (view v, chunk): grid view_grid[v] (or v) seen from pose[v] (igw_render.h: igw_render_views).  The caller has
+// only grids, at any row stride, so the block copies the view's 1,089 cells to LDS itself (16-byte loads where the
+// rows are aligned, bytes otherwise) and derives the occupancy bitmap there: one thread per (y, x) row of 11 cells
+// gathers the row's 11 bits and ORs them into the one or two words they fall in.
+__global__ __launch_bounds__(kThreads) void igw_render_views_kernel(
+    const int8_t* __restrict__ grids, int64_t grid_stride, int n_grids, const int32_t* __restrict__ view_grid,
+    const double* __restrict__ pose, const uint32_t* __restrict__ atlas, int side, uint8_t* __restrict__ out, int W,
+    int H, int C) {
+    __shared__ uint4 s_grid4[kGridStride / 16];
+    __shared__ uint4 s_occ4[kOccWords / 4];
+    __shared__ uint4 s_stage4[kChunk * 4 / 16];
+    const int tid = threadIdx.x;
+    const int64_t v = blockIdx.x;
+    // device-side values are not trusted: a view of a row outside the grids is not drawn
+    const int64_t row = view_grid ? (int64_t)view_grid[v] : v;
+    if (row < 0 || row >= n_grids) return;
+
+    int8_t* s_grid = reinterpret_cast<int8_t*>(s_grid4);
+    uint32_t* s_occ = reinterpret_cast<uint32_t*>(s_occ4);
+    const int8_t* g = grids + row * grid_stride;
+    if (((reinterpret_cast<uintptr_t>(grids) | (uintptr_t)grid_stride) & 15) == 0) {
+        // aligned rows have a stride >= 1104: the 15 bytes past the cells belong to the row
+        if (tid < kGridStride / 16) s_grid4[tid] = reinterpret_cast<const uint4*>(g)[tid];
+    } else {
+        for (int c = tid; c < kCells; c += kThreads) s_grid[c] = g[c];
+    }
+    if (tid < kOccWords) s_occ[tid] = 0u;
+    __syncthreads();
+    if (tid < 99) {   // include/igw.h: bit (y+1)*169 + (x+6)*13 + (z+6) of grid[y+1][x+5][z+5]
+        const int yv = tid / 11, xv = tid - yv * 11;
+        const int8_t* cells = s_grid + tid * 11;
+        uint32_t bits = 0;
+        for (int z = 0; z < 11; z++) bits |= (uint32_t)(cells[z] != 0) << z;
+        const int bit = yv * 169 + (xv + 1) * 13 + 1, sh = bit & 31;
+        if (bits) {
+            atomicOr(&s_occ[bit >> 5], bits << sh);
+            if (sh > 21 && (bits >> (32 - sh))) atomicOr(&s_occ[(bit >> 5) + 1], bits >> (32 - sh));
+        }
+    }
+    render_frame(pose + 5 * v, s_occ, s_grid, s_stage4, atlas, side, out, v, W, H, C);
+}
+
 thread_local char g_err[512] = "";
 
 int fail(int code, const char* fmt, const char* detail = "") {
@@ -187,6 +229,37 @@ int igw_render_episodes(const uint8_t* records, int64_t n_records, const int64_t
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess)
         return fail(IGW_RENDER_ERR_HIP, "igw_render_episodes: launch failed: %s", hipGetErrorString(e));
+    return IGW_RENDER_OK;
+}
+
+int igw_render_views(const int8_t* grids, int64_t grid_stride, int32_t n_grids, const int32_t* view_grid,
+                     const double* pose, int32_t m, const uint8_t* atlas, int32_t atlas_side, uint8_t* out,
+                     int32_t width, int32_t height, int32_t channels, void* stream) {
+    if (m < 0 || n_grids < 0) return fail(IGW_RENDER_ERR_INVALID, "igw_render_views: m and n_grids must be >= 0");
+    if (grid_stride < kCells) return fail(IGW_RENDER_ERR_INVALID, "igw_render_views: grid_stride must be >= 1089");
+    if (!view_grid && n_grids < m)
+        return fail(IGW_RENDER_ERR_INVALID, "igw_render_views: without view_grid, view v shows row v: n_grids must "
+                                            "be >= m");
+    if (channels != 3 && channels != 4)
+        return fail(IGW_RENDER_ERR_INVALID, "igw_render_views: channels must be 3 or 4");
+    if (width < 1 || width > IGW_RENDER_MAX_SIDE || height < 1 || height > IGW_RENDER_MAX_SIDE)
+        return fail(IGW_RENDER_ERR_INVALID, "igw_render_views: width and height must be in 1..1024");
+    if (atlas_side < 8 || atlas_side > IGW_RENDER_MAX_ATLAS || atlas_side % 8)
+        return fail(IGW_RENDER_ERR_INVALID, "igw_render_views: atlas_side must be a multiple of 8 in 8..256");
+    if (m > 0 && (!grids || !pose || !atlas || !out)) return fail(IGW_RENDER_ERR_INVALID, "igw_render_views: null buffer");
+    if (!aligned(view_grid, 4) || !aligned(pose, 8) || !aligned(atlas, 4))
+        return fail(IGW_RENDER_ERR_INVALID, "igw_render_views: pose must be 8-byte, view_grid and atlas 4-byte "
+                                            "aligned");
+    if (!have_device())
+        return fail(IGW_RENDER_ERR_NO_DEVICE, "igw_render_views: no HIP device available (the renderer has no CPU fallback)");
+    if (m == 0) return IGW_RENDER_OK;
+    const int chunks = (width * height + kChunk - 1) / kChunk;
+    hipLaunchKernelGGL(igw_render_views_kernel, dim3((unsigned)m, (unsigned)chunks), dim3(kThreads), 0,
+                       (hipStream_t)stream, grids, grid_stride, (int)n_grids, view_grid, pose,
+                       reinterpret_cast<const uint32_t*>(atlas), (int)atlas_side, out, (int)width, (int)height,
+                       (int)channels);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(IGW_RENDER_ERR_HIP, "igw_render_views: launch failed: %s", hipGetErrorString(e));
     return IGW_RENDER_OK;
 }
 

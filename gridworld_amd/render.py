@@ -2,7 +2,8 @@
 
     from gridworld_amd import render
     atlas = render.load_atlas('texture.png')       # the reference's texture file, for the reference's look
-    frames = render.render_pov(env, out=None)       # or env.render_pov() / VecGridWorld(..., renderer='hip')
+    frames = env.render_pov()                       # or VecGridWorld(..., renderer='hip') for obs['pov']
+    views = gridworld_amd.render_views(grids, poses)    # any grid from any camera (gridworld_amd/visualizer.py)
 
 The renderer is a separate library: it reads the step path's state buffers (include/igw.h) and is not part of the
 step library's build (its sources and build id are its own, so the step library's profiles stay valid).  There is
@@ -29,7 +30,7 @@ MAX_ATLAS = 256
 MAX_EPISODE = 1 << 24
 CLEAR_RGBA = (128, 176, 255, 255)   # unorm8 of glClearColor(0.5, 0.69, 1.0, 1), gridworld/render.py:41
 EXPORTS = ['igw_render_version', 'igw_render_build_id', 'igw_render_last_error', 'igw_render_pov',
-           'igw_render_episodes']
+           'igw_render_episodes', 'igw_render_views']
 _MARK = b'igw-render-build-id:'
 
 
@@ -119,6 +120,8 @@ def load(build_if_missing=True):
     i64 = C.c_int64
     L.igw_render_episodes.argtypes = [vp, i64, vp, vp, vp, vp, vp, i32, i32, vp, i32, vp, i64, i32, i32, i32, vp]
     L.igw_render_episodes.restype = C.c_int
+    L.igw_render_views.argtypes = [vp, i64, i32, vp, vp, i32, vp, i32, vp, i32, i32, i32, vp]
+    L.igw_render_views.restype = C.c_int
     _lib = L
     return L
 
@@ -194,6 +197,15 @@ def render_episodes_into(records, n_records, first, length, frame0, start_grid, 
                                int(height), int(channels), stream)
     if rc:
         check(rc, 'igw_render_episodes')
+
+
+def render_views_into(grids, grid_stride, n_grids, view_grid, pose, m, atlas, out, width, height, channels, stream):
+    """One igw_render_views call on raw pointers (ints; view_grid may be None); `atlas` is a device tensor [S, S, 4]."""
+    L = load()
+    rc = L.igw_render_views(grids, int(grid_stride), int(n_grids), view_grid, pose, int(m), atlas.data_ptr(),
+                            int(atlas.shape[0]), out, int(width), int(height), int(channels), stream)
+    if rc:
+        check(rc, 'igw_render_views')
 
 
 if __name__ == '__main__':

@@ -417,6 +417,25 @@ class VecGridWorld:
         return _render_rows(self, self.agent_buf, self.grid_buf, self.occ_buf, self.num_envs, out, channels, size,
                             self._stream())
 
+    def render_views(self, poses, rows=None, what='grid', **kw):
+        """Views of the batch from cameras of the caller's choice (visualizer.render_views): uint8 [M, H, W, channels]
+        for poses [M, 5] float64 (x, y, z, yaw, pitch).  what='grid': the envs' CURRENT grids, read in place from
+        grid_buf, `rows` = the env of each view (the spectator camera); what='target' / 'start': the target / starting
+        grid of task-table rows, `rows` = the task row of each view (the goal image; env_task maps envs to rows; the
+        table's target is the one the reward counts: the task's target grid, less its starting grid if it has one).
+        rows=None: view v shows row v.  One launch on the current stream, with the env's atlas and render_size unless
+        `atlas` / `size` say otherwise; `channels` and `out` as for render_pov.  It keeps no frame tensor, so it needs
+        no renderer='hip' at construction."""
+        from . import visualizer as V
+        try:
+            grids = {'grid': self.grid_buf, 'target': self.task_target, 'start': self.task_start}[what]
+        except KeyError:
+            raise ValueError(f"what must be 'grid', 'target' or 'start', got {what!r}") from None
+        kw.setdefault('size', self.render_size)
+        if kw.get('atlas') is None:
+            kw['atlas'] = self._atlas()
+        return V.render_views(grids, poses, view_grid=rows, device=self.device, **kw)
+
     # ---- a captured step loop (the loop of examples/run_env.py:18-26 as ONE HIP-graph launch) ----
     def capture_steps(self, actions, record=False, chains=1):
         """Captures `for t in range(T): env.step(actions[t])` into a HIP graph and returns a StepGraph; replay() launches

@@ -80,6 +80,30 @@ int igw_render_episodes(const uint8_t* records, int64_t n_records, const int64_t
                         int32_t max_length, const uint8_t* atlas, int32_t atlas_side, uint8_t* out, int64_t n_frames,
                         int32_t width, int32_t height, int32_t channels, void* stream);
 
+/*
+ * Renders m views into out [m][height][width][channels] uint8, in one launch: view v shows grid view_grid[v] from
+ * pose[v].  Neither the camera nor the scene is tied to an env: any grid from any pose (the reference's
+ * gridworld/visualizer.py), e.g. goal images, spectator cameras of a running batch, orbits of one structure.
+ *   grids      [n_grids] rows of int8 cells [y+1][x+5][z+5], row r starting at grids + r * grid_stride elements
+ *              (grid_stride >= 1089: 1089 for a dense [G, 9, 11, 11] array, 1104 for the step path's grid_buf,
+ *              task_target and task_start of include/igw.h, which are read in place).  A cell is occupied iff it is
+ *              not 0; ids outside 1..6 are drawn as the nearer of 1 and 6, as by igw_render_pov.  No alignment is
+ *              required; rows whose base and stride are multiples of 16 bytes are fetched with 16-byte loads.
+ *   view_grid  [m] i32 row of each view, or NULL: view v shows row v (then n_grids >= m)
+ *   pose       [m][5] f64 x, y, z, yaw, pitch (degrees; the order of an agent record and of init_pose)
+ * The occupancy bitmap is derived from the grid on the device, so there is no occupancy input.  For a grid with ids
+ * 0..6, view v is bit-identical to what igw_render_pov draws for an agent record holding pose[v] over that grid with
+ * its matching bitmap (the same per-block body).  The eye may be anywhere: outside the build zone, beyond the ground,
+ * below it (then the ground is not drawn: it has a top face only); surfaces beyond depth 30 are clipped as always.
+ * Every array is a device array and is read on the device only: the call never reads it on the host, never
+ * allocates, never synchronises.  Device-side values are not trusted: a view whose view_grid[v] is outside
+ * [0, n_grids) is not drawn (its frame is left unwritten).  Atlas, size and channels as for igw_render_pov.
+ * m == 0 is a no-op.  Frames are written with 64-bit offsets.
+ */
+int igw_render_views(const int8_t* grids, int64_t grid_stride, int32_t n_grids, const int32_t* view_grid,
+                     const double* pose, int32_t m, const uint8_t* atlas, int32_t atlas_side, uint8_t* out,
+                     int32_t width, int32_t height, int32_t channels, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,14 @@ for --episodes envs (default 4,096 x 250: 1.03 M frames of 64 x 64 RGB):
 
     python tools/bench_render.py --mode episodes [--out profiles/r08_render_episodes_bench.json]
 
+--mode views measures the free-camera views (igw_render_views), each shape one launch, and, in the same process,
+igw_render_pov on as many 64 x 64 frames as shape (a) as the yardstick, --repeats times each for the run-to-run spread:
+
+  a  4,096 grids x 8 look-at views at 64 x 64     b  64 grids x 8 views at 512 x 512     c  1 grid x 180 orbit views at
+  640 x 640: ms per launch, frames / s, megapixels / s
+
+    python tools/bench_render.py --mode views [--out profiles/r09_render_views_bench.json]
+
 The VALU side of the kernel comes from a separate profiler run ("First-person frames": measured numbers).
 """
 import argparse
@@ -173,6 +181,65 @@ def bench_episodes(n, steps, iters, warmup):
     return res
 
 
+def _spread(us):
+    return {'us_per_launch_median': round(float(np.median(us)), 1), 'us_per_launch_min': round(min(us), 1),
+            'us_per_launch_max': round(max(us), 1), 'repeats': len(us)}
+
+
+def bench_views(iters, warmup, repeats):
+    import gridworld_amd as G
+    from gridworld_amd import workloads
+    dev = torch.device('cuda', torch.cuda.current_device())
+    atlas = torch.from_numpy(G.render.default_atlas()).to(dev)
+    centre = (0.0, 1.5, 0.0)
+    shapes = (('a', 4096, 8, (64, 64), G.orbit_poses(centre, 12, 4.5, 8, phase=10)),
+              ('b', 64, 8, (512, 512), G.orbit_poses(centre, 12, 4.5, 8, phase=10)),
+              ('c', 1, 180, (640, 640), G.orbit_poses(centre, 14, 5.5, 180)))
+    res = {}
+    for name, n_grids, per_grid, (W, H), ring in shapes:
+        grids = workloads.uniform20(n_grids, seed=6).to(device=dev, dtype=torch.int8).reshape(n_grids, 1089).contiguous()
+        m = n_grids * per_grid
+        poses = torch.from_numpy(np.tile(ring, (n_grids, 1))).to(dev)
+        view_grid = torch.arange(n_grids, dtype=torch.int32, device=dev).repeat_interleave(per_grid)
+        out = torch.empty((m, H, W, 3), dtype=torch.uint8, device=dev)
+        it = max(3, iters // 5) if W > 64 else iters
+        us = [_time(lambda: G.render_views(grids, poses, view_grid=view_grid, size=(W, H), atlas=atlas, out=out), it,
+                    warmup) for _ in range(repeats)]
+        med = float(np.median(us))
+        res[name] = dict(_spread(us), grids=n_grids, views=m, size=[W, H], channels=3,
+                         ms_per_launch=round(med * 1e-3, 3), frames_per_s=round(m / (med * 1e-6), 1),
+                         megapixels_per_s=round(m * W * H / med, 1))
+        del out
+        torch.cuda.empty_cache()
+    # the yardstick: igw_render_pov on as many 64 x 64 frames as (a), eyes inside the zone (a task's init_pose)
+    n = 4096 * 8
+    env = _batch(n)
+    out = torch.empty((n, 64, 64, 3), dtype=torch.uint8, device=dev)
+    us = [_time(lambda: env.render_pov(out=out), iters, warmup) for _ in range(repeats)]
+    med = float(np.median(us))
+    res['pov_yardstick'] = dict(_spread(us), envs=n, size=[64, 64], channels=3, ms_per_launch=round(med * 1e-3, 3),
+                                frames_per_s=round(n / (med * 1e-6), 1), megapixels_per_s=round(n * 4096 / med, 1))
+    # the same scenes both ways: the views kernel on the batch's own grids from the agents' own poses
+    torch.cuda.synchronize()
+    own = torch.from_numpy(np.ascontiguousarray(env.agent_buf.cpu().numpy()[:, :40]).view(np.float64)).to(dev)
+    us = [_time(lambda: env.render_views(own, out=out), iters, warmup) for _ in range(repeats)]
+    med = float(np.median(us))
+    res['views_of_the_yardstick_scenes'] = dict(_spread(us), views=n, size=[64, 64], channels=3,
+                                                ms_per_launch=round(med * 1e-3, 3),
+                                                frames_per_s=round(n / (med * 1e-6), 1),
+                                                megapixels_per_s=round(n * 4096 / med, 1))
+    return res
+
+
+def _git_commit():
+    import subprocess
+    try:
+        return subprocess.check_output(['git', 'rev-parse', 'HEAD'], cwd=ROOT, text=True,
+                                       stderr=subprocess.DEVNULL).strip()
+    except (OSError, subprocess.CalledProcessError):
+        return None
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--envs', default='1,4096,65536,524288')
@@ -181,7 +248,9 @@ def main():
     ap.add_argument('--facade-steps', type=int, default=500)
     ap.add_argument('--skip', default='', help='comma list of parts to skip: step, facade')
     ap.add_argument('--out', default=None)
-    ap.add_argument('--mode', default='render', choices=('render', 'episodes'))
+    ap.add_argument('--mode', default='render', choices=('render', 'episodes', 'views'))
+    ap.add_argument('--repeats', type=int, default=5, help='--mode views: repeats of every measurement')
+    ap.add_argument('--git-commit', default=None, help='--mode views: the commit to stamp (default: git rev-parse)')
     ap.add_argument('--episodes', type=int, default=4096)
     ap.add_argument('--steps', type=int, default=250)
     a = ap.parse_args()
@@ -191,6 +260,10 @@ def main():
     skip = set(filter(None, a.skip.split(',')))
     line = {'tool': 'tools/bench_render.py', 'render_build_id': R.build_id(), 'step_build_id': B.source_hash(),
             'device': torch.cuda.get_device_name(0)}
+    if a.mode == 'views':
+        line['git_commit'] = a.git_commit or _git_commit()
+        line['views'] = bench_views(a.iters, a.warmup, max(1, a.repeats))
+        return _emit(line, a.out)
     if a.mode == 'episodes':
         line['episodes'] = bench_episodes(a.episodes, a.steps, a.iters, a.warmup)
         return _emit(line, a.out)
