@@ -5,7 +5,6 @@ entry point raises.
 """
 import ctypes as C
 import os
-import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'libigw_hip.so')
@@ -74,13 +73,7 @@ def load(build_if_missing=True):
         path, build_if_missing = os.environ['IGW_LIB'], False
     if build_if_missing:
         from . import build as _build
-        try:
-            _build.build(diag=diag)
-        except subprocess.CalledProcessError as e:  # a compile error must never fall back to a stale binary
-            raise IgwError(f'hipcc failed to build {os.path.basename(path)}: {e}') from e
-        except Exception as e:  # no hipcc: an existing library is still usable, a missing one is fatal
-            if not os.path.exists(path):
-                raise IgwError(f'{os.path.basename(path)} is missing and could not be built: {e}') from e
+        (_build.DIAG if diag else _build.STEP).build_for_load(IgwError)
     if not os.path.exists(path):
         raise IgwError(f'{os.path.basename(path)} not found; run `python -m gridworld_amd.build`')
     L = C.CDLL(path)

@@ -34,69 +34,113 @@ def hipcc():
     raise RuntimeError('hipcc not found')
 
 
+class Library:
+    """One hipcc-built shared library: where it goes, what it is made of, and how its build id is stamped into it.
+    `sources` and `headers` are file names (relative ones are looked up under `root`); `marker` is the string that
+    precedes the id inside the file and `define` the macro that carries marker + id into the source; `flags` are
+    added to FLAGS on the command line and `suffix` to the id; `deps` are further files a build is older than when
+    it is stale (the module that describes the library)."""
+
+    def __init__(self, lib, sources, headers, marker, define, root='', flags=(), suffix='', deps=()):
+        self.lib, self.sources, self.headers, self.marker, self.define = lib, sources, headers, marker.encode(), define
+        self.root, self.flags, self.suffix, self.deps = root, tuple(flags), suffix, [os.path.abspath(d) for d in deps]
+
+    def path(self, name):
+        return os.path.join(self.root, name)
+
+    def source_hash(self):
+        """Identity of a build: sha256 over the sources and headers (sorted by name; base name, NUL, contents) and the
+        compiler FLAGS, 16 hex digits, plus the suffix."""
+        import hashlib
+        h = hashlib.sha256()
+        for f in sorted(self.sources + self.headers):
+            h.update(os.path.basename(f).encode() + b'\0')
+            with open(self.path(f), 'rb') as fh:
+                h.update(fh.read())
+        h.update(' '.join(FLAGS).encode())
+        return h.hexdigest()[:16] + self.suffix
+
+    def built_id(self, lib=None):
+        """The build id of an existing library file, read without loading it (the id string follows the marker)."""
+        try:
+            with open(lib or self.lib, 'rb') as f:
+                data = f.read()
+            i = data.find(self.marker)
+            if i < 0:
+                return None
+            return data[i + len(self.marker):data.index(b'\0', i)].decode()
+        except (OSError, ValueError):
+            return None
+
+    def is_stale(self, lib=None):
+        """Missing, older than a source (mtime), or built from other sources than the ones on disk (build id)."""
+        lib = lib or self.lib
+        if not os.path.exists(lib):
+            return True
+        t = os.path.getmtime(lib)
+        deps = [self.path(f) for f in self.sources + self.headers] + self.deps
+        return any(os.path.getmtime(d) > t for d in deps) or self.built_id(lib) != self.source_hash()
+
+    def build(self, force=False, extra_flags=(), verbose=False):
+        """Compiles under an exclusive file lock and installs the result with an atomic rename, so several
+        ranks starting at once (torchrun) never see or write a half-built library."""
+        lib = self.lib
+        if not force and not self.is_stale():
+            return lib
+        import fcntl
+        with open(lib + '.lock', 'w') as lock:
+            fcntl.flock(lock, fcntl.LOCK_EX)
+            try:
+                if not force and not self.is_stale():  # another process built it while we waited
+                    return lib
+                tmp = f'{lib}.tmp.{os.getpid()}'
+                stamp = '-D%s="%s%s"' % (self.define, self.marker.decode(), self.source_hash())
+                cmd = ([hipcc()] + FLAGS + list(extra_flags) + list(self.flags) + [stamp, '-o', tmp]
+                       + [self.path(s) for s in self.sources])
+                if verbose:
+                    print(' '.join(cmd))
+                subprocess.run(cmd, check=True)
+                os.replace(tmp, lib)
+            finally:
+                fcntl.flock(lock, fcntl.LOCK_UN)
+        return lib
+
+    def build_for_load(self, error):
+        """The rule of a binding that builds before it loads: a compile error raises `error` (never a fall back to a
+        stale binary); without a compiler an existing library is still usable, a missing one is fatal."""
+        name = os.path.basename(self.lib)
+        try:
+            self.build()
+        except subprocess.CalledProcessError as e:
+            raise error(f'hipcc failed to build {name}: {e}') from e
+        except Exception as e:
+            if not os.path.exists(self.lib):
+                raise error(f'{name} is missing and could not be built: {e}') from e
+
+
+# The step library and its diagnostic variant (libigw_hip_diag.so, -DIGW_DIAG, next to the production library).  The
+# id is compiled into the library (-DIGW_BUILD_ID, exported as igw_build_id()) and stamped on every profile summary
+# under profiles/ (tools/summarize_profile.py), so a bench line can tell whether the PMC bytes it quotes were measured
+# on the kernels it timed.
+STEP = Library(LIB, SOURCES, HEADERS, 'igw-build-id:', 'IGW_BUILD_ID', root=CSRC, deps=[__file__])
+DIAG = Library(LIB_DIAG, SOURCES, HEADERS, 'igw-build-id:', 'IGW_BUILD_ID', root=CSRC, flags=['-DIGW_DIAG'],
+               suffix='-diag', deps=[__file__])
+
+
 def source_hash(diag=False):
-    """Identity of a kernel build: sha256 over the kernel sources, include/igw.h and the compiler flags (16 hex
-    digits).  It is compiled into the library (-DIGW_BUILD_ID, exported as igw_build_id()) and stamped on every
-    profile summary under profiles/ (tools/summarize_profile.py), so a bench line can tell whether the PMC bytes it
-    quotes were measured on the kernels it timed."""
-    import hashlib
-    h = hashlib.sha256()
-    for f in sorted(SOURCES + HEADERS):
-        h.update(os.path.basename(f).encode() + b'\0')
-        with open(os.path.join(CSRC, f), 'rb') as fh:
-            h.update(fh.read())
-    h.update(' '.join(FLAGS).encode())
-    return h.hexdigest()[:16] + ('-diag' if diag else '')
+    return (DIAG if diag else STEP).source_hash()
 
 
 def built_id(lib=LIB):
-    """igw_build_id() of an existing library file, read without loading it (the id string follows a marker)."""
-    try:
-        with open(lib, 'rb') as f:
-            data = f.read()
-        i = data.find(b'igw-build-id:')
-        if i < 0:
-            return None
-        j = data.index(b'\0', i)
-        return data[i + len(b'igw-build-id:'):j].decode()
-    except (OSError, ValueError):
-        return None
+    return STEP.built_id(lib)
 
 
 def is_stale(lib=LIB, diag=False):
-    """Missing, older than a source (mtime), or built from other sources than the ones on disk (build id)."""
-    if not os.path.exists(lib):
-        return True
-    t = os.path.getmtime(lib)
-    deps = [os.path.join(CSRC, f) for f in SOURCES + HEADERS] + [os.path.abspath(__file__)]
-    return any(os.path.getmtime(d) > t for d in deps) or built_id(lib) != source_hash(diag)
+    return (DIAG if diag else STEP).is_stale(lib)
 
 
 def build(force=False, extra_flags=(), verbose=False, diag=False):
-    """Compiles under an exclusive file lock and installs the result with an atomic rename, so several
-    ranks starting at once (torchrun) never see or write a half-built library.  diag=True builds the
-    diagnostic variant (libigw_hip_diag.so, -DIGW_DIAG) next to the production library."""
-    lib = LIB_DIAG if diag else LIB
-    if diag:
-        extra_flags = tuple(extra_flags) + ('-DIGW_DIAG',)
-    extra_flags = tuple(extra_flags) + ('-DIGW_BUILD_ID="igw-build-id:%s"' % source_hash(diag),)
-    if not force and not is_stale(lib, diag):
-        return lib
-    import fcntl
-    with open(lib + '.lock', 'w') as lock:
-        fcntl.flock(lock, fcntl.LOCK_EX)
-        try:
-            if not force and not is_stale(lib, diag):  # another process built it while we waited
-                return lib
-            tmp = f'{lib}.tmp.{os.getpid()}'
-            cmd = [hipcc()] + FLAGS + list(extra_flags) + ['-o', tmp] + [os.path.join(CSRC, s) for s in SOURCES]
-            if verbose:
-                print(' '.join(cmd))
-            subprocess.run(cmd, check=True)
-            os.replace(tmp, lib)
-        finally:
-            fcntl.flock(lock, fcntl.LOCK_UN)
-    return lib
+    return (DIAG if diag else STEP).build(force, extra_flags, verbose)
 
 
 if __name__ == '__main__':

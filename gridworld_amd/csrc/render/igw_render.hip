@@ -23,9 +23,6 @@ __global__ __launch_bounds__(kThreads) void igw_render_pov_kernel(const uint8_t*
                                                               const uint32_t* __restrict__ occ,
                                                               const uint32_t* __restrict__ atlas, int side,
                                                               uint8_t* __restrict__ out, int W, int H, int C) {
-    __shared__ uint4 s_grid4[kGridStride / 16];
-    __shared__ uint4 s_occ4[kOccWords / 4];
-    __shared__ uint4 s_stage4[kChunk * 4 / 16];
     const int tid = threadIdx.x;
     const int64_t env = blockIdx.x;
     if (tid < kGridStride / 16)
@@ -33,22 +30,18 @@ __global__ __launch_bounds__(kThreads) void igw_render_pov_kernel(const uint8_t*
     else if (tid >= 128 && tid < 128 + kOccWords / 4)
         s_occ4[tid - 128] = reinterpret_cast<const uint4*>(occ + env * kOccWords)[tid - 128];
     const double* pose = reinterpret_cast<const double*>(agent + env * kAgentBytes);
-    render_frame(pose, reinterpret_cast<const uint32_t*>(s_occ4), reinterpret_cast<const int8_t*>(s_grid4), s_stage4,
-                 atlas, side, out, env, W, H, C);
+    render_frame(pose, lds_occ(), lds_grid(), s_stage4, atlas, side, out, env, W, H, C);
 }
 
 // Block (episode e, entry t, chunk): frame t of episode e, rebuilt from the episode log (igw_render.h:
 // igw_render_episodes).  The grid is the start grid with the last change of every cell among records 0..t-1 applied:
 // one strided pass over the records keeps, per cell, max(record << 3 | colour) in an LDS table (the staging area,
-// free until the pixels are shaded); the occupancy bitmap is then derived from the grid.
+// free until the pixels are shaded); the occupancy bitmap is then derived from the grid (build_occ).
 __global__ __launch_bounds__(kThreads) void igw_render_episodes_kernel(
     const uint8_t* __restrict__ records, int64_t n_records, const int64_t* __restrict__ first,
     const int32_t* __restrict__ length, const int64_t* __restrict__ frame0, const int8_t* __restrict__ start_grid,
-    const double* __restrict__ init_pose, int max_length, const uint32_t* __restrict__ atlas, int side,
-    uint8_t* __restrict__ out, int64_t n_frames, int W, int H, int C) {
-    __shared__ uint4 s_grid4[kGridStride / 16];
-    __shared__ uint4 s_occ4[kOccWords / 4];
-    __shared__ uint4 s_stage4[kChunk * 4 / 16];
+    const double* __restrict__ init_pose, int max_length, int64_t n_frames, const uint32_t* __restrict__ atlas,
+    int side, uint8_t* __restrict__ out, int W, int H, int C) {
     const int tid = threadIdx.x;
     const int64_t e = blockIdx.x / (unsigned)(max_length + 1);
     const int t = (int)(blockIdx.x - e * (max_length + 1));
@@ -58,8 +51,7 @@ __global__ __launch_bounds__(kThreads) void igw_render_episodes_kernel(
     if (t > len || r0 < 0 || r0 > n_records - len || f0 < 0 || f0 > n_frames - (len + 1)) return;
 
     int* s_last = reinterpret_cast<int*>(s_stage4);
-    int8_t* s_grid = reinterpret_cast<int8_t*>(s_grid4);
-    uint32_t* s_occ = reinterpret_cast<uint32_t*>(s_occ4);
+    int8_t* s_grid = lds_grid();
     if (tid < kGridStride / 16) s_grid4[tid] = reinterpret_cast<const uint4*>(start_grid + e * kGridStride)[tid];
     for (int c = tid; c < kCells; c += kThreads) s_last[c] = -1;
     // entry 0: the reset pose (f64, task_meta order x, y, z, yaw, pitch); entry t: the f32 agentPos of record t-1
@@ -83,38 +75,24 @@ __global__ __launch_bounds__(kThreads) void igw_render_episodes_kernel(
         const int w = s_last[c];
         if (w >= 0) s_grid[c] = (int8_t)(w & 7);
     }
-    __syncthreads();
-    if (tid < kOccWords) {   // include/igw.h: bit (y+1)*169 + (x+6)*13 + (z+6) of grid[y+1][x+5][z+5]
-        uint32_t bits = 0;
-        for (int b = 0; b < 32; b++) {
-            const int i = tid * 32 + b, yv = i / 169, r = i - yv * 169, xp = r / 13, zp = r - xp * 13;
-            if (yv < 9 && xp >= 1 && xp <= 11 && zp >= 1 && zp <= 11 && s_grid[yv * 121 + (xp - 1) * 11 + (zp - 1)] != 0)
-                bits |= 1u << b;
-        }
-        s_occ[tid] = bits;
-    }
-    render_frame(pose, s_occ, s_grid, s_stage4, atlas, side, out, f0 + t, W, H, C);
+    build_occ(s_grid, lds_occ());
+    render_frame(pose, lds_occ(), s_grid, s_stage4, atlas, side, out, f0 + t, W, H, C);
 }
 
 // Block (view v, chunk): grid view_grid[v] (or v) seen from pose[v] (igw_render.h: igw_render_views).  The caller has
 // only grids, at any row stride, so the block copies the view's 1,089 cells to LDS itself (16-byte loads where the
-// rows are aligned, bytes otherwise) and derives the occupancy bitmap there: one thread per (y, x) row of 11 cells
-// gathers the row's 11 bits and ORs them into the one or two words they fall in.
+// rows are aligned, bytes otherwise) and derives the occupancy bitmap there (build_occ).
 __global__ __launch_bounds__(kThreads) void igw_render_views_kernel(
     const int8_t* __restrict__ grids, int64_t grid_stride, int n_grids, const int32_t* __restrict__ view_grid,
     const double* __restrict__ pose, const uint32_t* __restrict__ atlas, int side, uint8_t* __restrict__ out, int W,
     int H, int C) {
-    __shared__ uint4 s_grid4[kGridStride / 16];
-    __shared__ uint4 s_occ4[kOccWords / 4];
-    __shared__ uint4 s_stage4[kChunk * 4 / 16];
     const int tid = threadIdx.x;
     const int64_t v = blockIdx.x;
     // device-side values are not trusted: a view of a row outside the grids is not drawn
     const int64_t row = view_grid ? (int64_t)view_grid[v] : v;
     if (row < 0 || row >= n_grids) return;
 
-    int8_t* s_grid = reinterpret_cast<int8_t*>(s_grid4);
-    uint32_t* s_occ = reinterpret_cast<uint32_t*>(s_occ4);
+    int8_t* s_grid = lds_grid();
     const int8_t* g = grids + row * grid_stride;
     if (((reinterpret_cast<uintptr_t>(grids) | (uintptr_t)grid_stride) & 15) == 0) {
         // aligned rows have a stride >= 1104: the 15 bytes past the cells belong to the row
@@ -122,26 +100,14 @@ __global__ __launch_bounds__(kThreads) void igw_render_views_kernel(
     } else {
         for (int c = tid; c < kCells; c += kThreads) s_grid[c] = g[c];
     }
-    if (tid < kOccWords) s_occ[tid] = 0u;
-    __syncthreads();
-    if (tid < 99) {   // include/igw.h: bit (y+1)*169 + (x+6)*13 + (z+6) of grid[y+1][x+5][z+5]
-        const int yv = tid / 11, xv = tid - yv * 11;
-        const int8_t* cells = s_grid + tid * 11;
-        uint32_t bits = 0;
-        for (int z = 0; z < 11; z++) bits |= (uint32_t)(cells[z] != 0) << z;
-        const int bit = yv * 169 + (xv + 1) * 13 + 1, sh = bit & 31;
-        if (bits) {
-            atomicOr(&s_occ[bit >> 5], bits << sh);
-            if (sh > 21 && (bits >> (32 - sh))) atomicOr(&s_occ[(bit >> 5) + 1], bits >> (32 - sh));
-        }
-    }
-    render_frame(pose + 5 * v, s_occ, s_grid, s_stage4, atlas, side, out, v, W, H, C);
+    build_occ(s_grid, lds_occ());
+    render_frame(pose + 5 * v, lds_occ(), s_grid, s_stage4, atlas, side, out, v, W, H, C);
 }
 
 thread_local char g_err[512] = "";
 
-int fail(int code, const char* fmt, const char* detail = "") {
-    snprintf(g_err, sizeof(g_err), fmt, detail);
+int fail(int code, const char* entry, const char* what, const char* detail = "") {
+    snprintf(g_err, sizeof(g_err), "%s: %s%s", entry, what, detail);
     return code;
 }
 
@@ -155,6 +121,30 @@ bool have_device() {
         seen = 1;
     }
     return true;
+}
+
+// What every entry point does once its own arguments (counts, nulls, alignments, ranges) are in order: the checks of
+// the frame's shape and the atlas, the device, the empty launch, and the launch of `count` x chunks blocks of
+// kernel(own..., atlas, side, out, W, H, C).  An invalid argument (-1) comes before a missing device (-2), which
+// comes before the no-op of count == 0.
+template <typename... Params, typename... Own>
+int launch(const char* entry, void (*kernel)(Params...), int64_t count, const uint8_t* atlas, int32_t atlas_side,
+           uint8_t* out, int32_t width, int32_t height, int32_t channels, void* stream, Own... own) {
+    if (channels != 3 && channels != 4) return fail(IGW_RENDER_ERR_INVALID, entry, "channels must be 3 or 4");
+    if (width < 1 || width > IGW_RENDER_MAX_SIDE || height < 1 || height > IGW_RENDER_MAX_SIDE)
+        return fail(IGW_RENDER_ERR_INVALID, entry, "width and height must be in 1..1024");
+    if (atlas_side < 8 || atlas_side > IGW_RENDER_MAX_ATLAS || atlas_side % 8)
+        return fail(IGW_RENDER_ERR_INVALID, entry, "atlas_side must be a multiple of 8 in 8..256");
+    if (!have_device())
+        return fail(IGW_RENDER_ERR_NO_DEVICE, entry, "no HIP device available (the renderer has no CPU fallback)");
+    if (count == 0) return IGW_RENDER_OK;
+    const int chunks = (width * height + kChunk - 1) / kChunk;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)count, (unsigned)chunks), dim3(kThreads), 0, (hipStream_t)stream, own...,
+                       reinterpret_cast<const uint32_t*>(atlas), (int)atlas_side, out, (int)width, (int)height,
+                       (int)channels);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(IGW_RENDER_ERR_HIP, entry, "launch failed: ", hipGetErrorString(e));
+    return IGW_RENDER_OK;
 }
 
 }  // namespace
@@ -172,95 +162,50 @@ const char* igw_render_last_error(void) { return g_err; }
 
 int igw_render_pov(const void* agent, const int8_t* grid, const uint32_t* occ, int32_t n, const uint8_t* atlas,
                    int32_t atlas_side, uint8_t* out, int32_t width, int32_t height, int32_t channels, void* stream) {
-    if (n < 0) return fail(IGW_RENDER_ERR_INVALID, "igw_render_pov: n must be >= 0");
-    if (channels != 3 && channels != 4) return fail(IGW_RENDER_ERR_INVALID, "igw_render_pov: channels must be 3 or 4");
-    if (width < 1 || width > IGW_RENDER_MAX_SIDE || height < 1 || height > IGW_RENDER_MAX_SIDE)
-        return fail(IGW_RENDER_ERR_INVALID, "igw_render_pov: width and height must be in 1..1024");
-    if (atlas_side < 8 || atlas_side > IGW_RENDER_MAX_ATLAS || atlas_side % 8)
-        return fail(IGW_RENDER_ERR_INVALID, "igw_render_pov: atlas_side must be a multiple of 8 in 8..256");
+    if (n < 0) return fail(IGW_RENDER_ERR_INVALID, __func__, "n must be >= 0");
     if (n > 0 && (!agent || !grid || !occ || !atlas || !out))
-        return fail(IGW_RENDER_ERR_INVALID, "igw_render_pov: null buffer");
+        return fail(IGW_RENDER_ERR_INVALID, __func__, "null buffer");
     if (!aligned(agent, 8) || !aligned(grid, 16) || !aligned(occ, 16) || !aligned(atlas, 4))
-        return fail(IGW_RENDER_ERR_INVALID, "igw_render_pov: agent must be 8-byte, grid and occ 16-byte, atlas "
-                                            "4-byte aligned");
-    if (!have_device())
-        return fail(IGW_RENDER_ERR_NO_DEVICE, "igw_render_pov: no HIP device available (the renderer has no CPU fallback)");
-    if (n == 0) return IGW_RENDER_OK;
-    const int chunks = (width * height + kChunk - 1) / kChunk;
-    hipLaunchKernelGGL(igw_render_pov_kernel, dim3((unsigned)n, (unsigned)chunks), dim3(kThreads), 0,
-                       (hipStream_t)stream, static_cast<const uint8_t*>(agent), grid, occ,
-                       reinterpret_cast<const uint32_t*>(atlas), (int)atlas_side, out, (int)width, (int)height,
-                       (int)channels);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(IGW_RENDER_ERR_HIP, "igw_render_pov: launch failed: %s", hipGetErrorString(e));
-    return IGW_RENDER_OK;
+        return fail(IGW_RENDER_ERR_INVALID, __func__, "agent must be 8-byte, grid and occ 16-byte, atlas 4-byte "
+                                                      "aligned");
+    return launch(__func__, igw_render_pov_kernel, n, atlas, atlas_side, out, width, height, channels, stream,
+                  static_cast<const uint8_t*>(agent), grid, occ);
 }
 
 int igw_render_episodes(const uint8_t* records, int64_t n_records, const int64_t* first, const int32_t* length,
                         const int64_t* frame0, const int8_t* start_grid, const double* init_pose, int32_t m,
                         int32_t max_length, const uint8_t* atlas, int32_t atlas_side, uint8_t* out, int64_t n_frames,
                         int32_t width, int32_t height, int32_t channels, void* stream) {
-    if (m < 0) return fail(IGW_RENDER_ERR_INVALID, "igw_render_episodes: m must be >= 0");
+    if (m < 0) return fail(IGW_RENDER_ERR_INVALID, __func__, "m must be >= 0");
     if (max_length < 0 || max_length > IGW_RENDER_MAX_EPISODE)
-        return fail(IGW_RENDER_ERR_INVALID, "igw_render_episodes: max_length must be in 0..2^24");
+        return fail(IGW_RENDER_ERR_INVALID, __func__, "max_length must be in 0..2^24");
     if ((int64_t)m * (max_length + 1) > INT32_MAX)
-        return fail(IGW_RENDER_ERR_INVALID, "igw_render_episodes: m * (max_length + 1) must be < 2^31");
+        return fail(IGW_RENDER_ERR_INVALID, __func__, "m * (max_length + 1) must be < 2^31");
     if (n_records < 0 || n_frames < 0)
-        return fail(IGW_RENDER_ERR_INVALID, "igw_render_episodes: n_records and n_frames must be >= 0");
-    if (channels != 3 && channels != 4)
-        return fail(IGW_RENDER_ERR_INVALID, "igw_render_episodes: channels must be 3 or 4");
-    if (width < 1 || width > IGW_RENDER_MAX_SIDE || height < 1 || height > IGW_RENDER_MAX_SIDE)
-        return fail(IGW_RENDER_ERR_INVALID, "igw_render_episodes: width and height must be in 1..1024");
-    if (atlas_side < 8 || atlas_side > IGW_RENDER_MAX_ATLAS || atlas_side % 8)
-        return fail(IGW_RENDER_ERR_INVALID, "igw_render_episodes: atlas_side must be a multiple of 8 in 8..256");
+        return fail(IGW_RENDER_ERR_INVALID, __func__, "n_records and n_frames must be >= 0");
     if (m > 0 && (!records || !first || !length || !frame0 || !start_grid || !init_pose || !atlas || !out))
-        return fail(IGW_RENDER_ERR_INVALID, "igw_render_episodes: null buffer");
+        return fail(IGW_RENDER_ERR_INVALID, __func__, "null buffer");
     if (!aligned(records, 16) || !aligned(first, 8) || !aligned(length, 4) || !aligned(frame0, 8) ||
         !aligned(start_grid, 16) || !aligned(init_pose, 8) || !aligned(atlas, 4))
-        return fail(IGW_RENDER_ERR_INVALID, "igw_render_episodes: records and start_grid must be 16-byte, first, "
-                                            "frame0 and init_pose 8-byte, length and atlas 4-byte aligned");
-    if (!have_device()) return fail(IGW_RENDER_ERR_NO_DEVICE, "igw_render_episodes: no HIP device available (the renderer has no CPU fallback)");
-    if (m == 0) return IGW_RENDER_OK;
-    const int chunks = (width * height + kChunk - 1) / kChunk;
-    hipLaunchKernelGGL(igw_render_episodes_kernel, dim3((unsigned)(m * (max_length + 1)), (unsigned)chunks),
-                       dim3(kThreads), 0, (hipStream_t)stream, records, n_records, first, length, frame0, start_grid,
-                       init_pose, (int)max_length, reinterpret_cast<const uint32_t*>(atlas), (int)atlas_side, out,
-                       n_frames, (int)width, (int)height, (int)channels);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-        return fail(IGW_RENDER_ERR_HIP, "igw_render_episodes: launch failed: %s", hipGetErrorString(e));
-    return IGW_RENDER_OK;
+        return fail(IGW_RENDER_ERR_INVALID, __func__, "records and start_grid must be 16-byte, first, frame0 and "
+                                                      "init_pose 8-byte, length and atlas 4-byte aligned");
+    return launch(__func__, igw_render_episodes_kernel, (int64_t)m * (max_length + 1), atlas, atlas_side, out, width,
+                  height, channels, stream, records, n_records, first, length, frame0, start_grid, init_pose,
+                  (int)max_length, n_frames);
 }
 
 int igw_render_views(const int8_t* grids, int64_t grid_stride, int32_t n_grids, const int32_t* view_grid,
                      const double* pose, int32_t m, const uint8_t* atlas, int32_t atlas_side, uint8_t* out,
                      int32_t width, int32_t height, int32_t channels, void* stream) {
-    if (m < 0 || n_grids < 0) return fail(IGW_RENDER_ERR_INVALID, "igw_render_views: m and n_grids must be >= 0");
-    if (grid_stride < kCells) return fail(IGW_RENDER_ERR_INVALID, "igw_render_views: grid_stride must be >= 1089");
+    if (m < 0 || n_grids < 0) return fail(IGW_RENDER_ERR_INVALID, __func__, "m and n_grids must be >= 0");
+    if (grid_stride < kCells) return fail(IGW_RENDER_ERR_INVALID, __func__, "grid_stride must be >= 1089");
     if (!view_grid && n_grids < m)
-        return fail(IGW_RENDER_ERR_INVALID, "igw_render_views: without view_grid, view v shows row v: n_grids must "
-                                            "be >= m");
-    if (channels != 3 && channels != 4)
-        return fail(IGW_RENDER_ERR_INVALID, "igw_render_views: channels must be 3 or 4");
-    if (width < 1 || width > IGW_RENDER_MAX_SIDE || height < 1 || height > IGW_RENDER_MAX_SIDE)
-        return fail(IGW_RENDER_ERR_INVALID, "igw_render_views: width and height must be in 1..1024");
-    if (atlas_side < 8 || atlas_side > IGW_RENDER_MAX_ATLAS || atlas_side % 8)
-        return fail(IGW_RENDER_ERR_INVALID, "igw_render_views: atlas_side must be a multiple of 8 in 8..256");
-    if (m > 0 && (!grids || !pose || !atlas || !out)) return fail(IGW_RENDER_ERR_INVALID, "igw_render_views: null buffer");
+        return fail(IGW_RENDER_ERR_INVALID, __func__, "without view_grid, view v shows row v: n_grids must be >= m");
+    if (m > 0 && (!grids || !pose || !atlas || !out)) return fail(IGW_RENDER_ERR_INVALID, __func__, "null buffer");
     if (!aligned(view_grid, 4) || !aligned(pose, 8) || !aligned(atlas, 4))
-        return fail(IGW_RENDER_ERR_INVALID, "igw_render_views: pose must be 8-byte, view_grid and atlas 4-byte "
-                                            "aligned");
-    if (!have_device())
-        return fail(IGW_RENDER_ERR_NO_DEVICE, "igw_render_views: no HIP device available (the renderer has no CPU fallback)");
-    if (m == 0) return IGW_RENDER_OK;
-    const int chunks = (width * height + kChunk - 1) / kChunk;
-    hipLaunchKernelGGL(igw_render_views_kernel, dim3((unsigned)m, (unsigned)chunks), dim3(kThreads), 0,
-                       (hipStream_t)stream, grids, grid_stride, (int)n_grids, view_grid, pose,
-                       reinterpret_cast<const uint32_t*>(atlas), (int)atlas_side, out, (int)width, (int)height,
-                       (int)channels);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(IGW_RENDER_ERR_HIP, "igw_render_views: launch failed: %s", hipGetErrorString(e));
-    return IGW_RENDER_OK;
+        return fail(IGW_RENDER_ERR_INVALID, __func__, "pose must be 8-byte, view_grid and atlas 4-byte aligned");
+    return launch(__func__, igw_render_views_kernel, m, atlas, atlas_side, out, width, height, channels, stream, grids,
+                  grid_stride, (int)n_grids, view_grid, pose);
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
-// igw_render_frame.h -- the per-block body of the first-person ray caster, shared by every kernel of
-// libigw_render.so (igw_render.hip): the camera basis of one pose, and the pixels of one chunk of one frame from a
-// grid and occupancy bitmap already in LDS.  There is one ray caster; the kernels differ only in where the pose, the
-// grid and the bitmap come from.  The contract is DESIGN.md, section "First-person frames".
+// igw_render_frame.h -- what every kernel of libigw_render.so (igw_render.hip) shares: the block's LDS, the build of
+// the occupancy bitmap from a grid, and the per-block body of the first-person ray caster (the camera basis of one
+// pose, and the pixels of one chunk of one frame from a grid and occupancy bitmap already in LDS).  There is one ray
+// caster; the kernels differ only in where the pose, the grid and the bitmap come from.  The contract is DESIGN.md, section "First-person frames".
 #ifndef IGW_RENDER_FRAME_H
 #define IGW_RENDER_FRAME_H
 
@@ -32,6 +32,37 @@ __device__ __forceinline__ bool occupied(const uint32_t* occ, int cy, int cx, in
 __device__ __forceinline__ int texel_index(float u, int n) {   // GL_NEAREST texel of coordinate u in [0, 1] on n texels
     int k = (int)floorf(u * (float)n);
     return k < 0 ? 0 : k >= n ? n - 1 : k;
+}
+
+// The LDS of one block, declared once for every kernel: the env's grid, its occupancy bitmap, and the staging area
+// of the chunk's colours (free until the pixels are shaded: the episodes kernel keeps its replay table there).
+// 17,680 bytes.
+__shared__ uint4 s_grid4[kGridStride / 16];
+__shared__ uint4 s_occ4[kOccWords / 4];
+__shared__ uint4 s_stage4[kChunk * 4 / 16];
+
+__device__ __forceinline__ int8_t* lds_grid() { return reinterpret_cast<int8_t*>(s_grid4); }
+__device__ __forceinline__ uint32_t* lds_occ() { return reinterpret_cast<uint32_t*>(s_occ4); }
+
+// The occupancy bitmap of the grid in LDS (include/igw.h: bit (y+1)*169 + (x+6)*13 + (z+6) of grid[y+1][x+5][z+5]; a
+// cell is occupied iff it is not 0).  Every thread of the block calls it; its barrier publishes the caller's stores to
+// s_grid.  One thread per (y, x) row of 11 cells gathers the row's 11 bits and ORs them into the one or two words they
+// fall in.  The words are complete after the next barrier (the first one of render_frame()).
+__device__ __forceinline__ void build_occ(const int8_t* s_grid, uint32_t* s_occ) {
+    const int tid = threadIdx.x;
+    if (tid < kOccWords) s_occ[tid] = 0u;
+    __syncthreads();
+    if (tid < 99) {
+        const int yv = tid / 11, xv = tid - yv * 11;
+        const int8_t* cells = s_grid + tid * 11;
+        uint32_t bits = 0;
+        for (int z = 0; z < 11; z++) bits |= (uint32_t)(cells[z] != 0) << z;
+        const int bit = yv * 169 + (xv + 1) * 13 + 1, sh = bit & 31;
+        if (bits) {
+            atomicOr(&s_occ[bit >> 5], bits << sh);
+            if (sh > 21 && (bits >> (32 - sh))) atomicOr(&s_occ[(bit >> 5) + 1], bits >> (32 - sh));
+        }
+    }
 }
 
 // One chunk of one frame: pixels [c0, c0 + kChunk) of frame `frame` of `out` ([*][H][W][C], c0 = blockIdx.y *

@@ -10,9 +10,7 @@ step library's build (its sources and build id are its own, so the step library'
 no CPU fallback: without a HIP device every call raises.
 """
 import ctypes as C
-import hashlib
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -29,67 +27,29 @@ MAX_SIDE = 1024
 MAX_ATLAS = 256
 MAX_EPISODE = 1 << 24
 CLEAR_RGBA = (128, 176, 255, 255)   # unorm8 of glClearColor(0.5, 0.69, 1.0, 1), gridworld/render.py:41
-EXPORTS = ['igw_render_version', 'igw_render_build_id', 'igw_render_last_error', 'igw_render_pov',
-           'igw_render_episodes', 'igw_render_views']
-_MARK = b'igw-render-build-id:'
+_vp, _i32, _i64 = C.c_void_p, C.c_int32, C.c_int64
+# every symbol include/igw_render.h declares: (result, arguments)
+SIGNATURES = {
+    'igw_render_version': (C.c_int, []),
+    'igw_render_build_id': (C.c_char_p, []),
+    'igw_render_last_error': (C.c_char_p, []),
+    'igw_render_pov': (C.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp]),
+    'igw_render_episodes': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _i64, _i32, _i32,
+                                      _i32, _vp]),
+    'igw_render_views': (C.c_int, [_vp, _i64, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp]),
+}
+EXPORTS = list(SIGNATURES)
+# the library as build.py builds it: the step library's FLAGS, an id of its own (igw_render_build_id())
+LIBRARY = _build.Library(LIB, SOURCES, HEADERS, 'igw-render-build-id:', 'IGW_RENDER_BUILD_ID', deps=[__file__])
+source_hash, built_id, is_stale = LIBRARY.source_hash, LIBRARY.built_id, LIBRARY.is_stale
 
 
 class RenderError(RuntimeError):
     pass
 
 
-def source_hash():
-    """sha256 (16 hex digits) over the renderer's source, its header and the compiler flags: igw_render_build_id()."""
-    h = hashlib.sha256()
-    for f in sorted(SOURCES + HEADERS, key=os.path.basename):
-        h.update(os.path.basename(f).encode() + b'\0')
-        with open(f, 'rb') as fh:
-            h.update(fh.read())
-    h.update(' '.join(_build.FLAGS).encode())
-    return h.hexdigest()[:16]
-
-
-def built_id(lib=LIB):
-    """igw_render_build_id() of a library file, read without loading it."""
-    try:
-        with open(lib, 'rb') as f:
-            data = f.read()
-        i = data.find(_MARK)
-        if i < 0:
-            return None
-        return data[i + len(_MARK):data.index(b'\0', i)].decode()
-    except (OSError, ValueError):
-        return None
-
-
-def is_stale(lib=LIB):
-    if not os.path.exists(lib):
-        return True
-    t = os.path.getmtime(lib)
-    deps = SOURCES + HEADERS + [os.path.abspath(__file__)]
-    return any(os.path.getmtime(d) > t for d in deps) or built_id(lib) != source_hash()
-
-
 def build(force=False, verbose=False):
-    """hipcc with the step library's FLAGS, under an exclusive file lock, installed by an atomic rename."""
-    if not force and not is_stale():
-        return LIB
-    import fcntl
-    with open(LIB + '.lock', 'w') as lock:
-        fcntl.flock(lock, fcntl.LOCK_EX)
-        try:
-            if not force and not is_stale():
-                return LIB
-            tmp = f'{LIB}.tmp.{os.getpid()}'
-            cmd = ([_build.hipcc()] + _build.FLAGS + ['-DIGW_RENDER_BUILD_ID="igw-render-build-id:%s"' % source_hash(),
-                                                      '-o', tmp] + SOURCES)
-            if verbose:
-                print(' '.join(cmd))
-            subprocess.run(cmd, check=True)
-            os.replace(tmp, LIB)
-        finally:
-            fcntl.flock(lock, fcntl.LOCK_UN)
-    return LIB
+    return LIBRARY.build(force, verbose=verbose)
 
 
 _lib = None
@@ -101,27 +61,13 @@ def load(build_if_missing=True):
     if _lib is not None:
         return _lib
     if build_if_missing:
-        try:
-            build()
-        except subprocess.CalledProcessError as e:
-            raise RenderError(f'hipcc failed to build libigw_render.so: {e}') from e
-        except Exception as e:  # no hipcc: an existing library is still usable, a missing one is fatal
-            if not os.path.exists(LIB):
-                raise RenderError(f'libigw_render.so is missing and could not be built: {e}') from e
+        LIBRARY.build_for_load(RenderError)
     if not os.path.exists(LIB):
         raise RenderError('libigw_render.so not found; run `python -m gridworld_amd.render`')
     L = C.CDLL(LIB)
-    vp, i32 = C.c_void_p, C.c_int32
-    L.igw_render_version.restype = C.c_int
-    L.igw_render_build_id.restype = C.c_char_p
-    L.igw_render_last_error.restype = C.c_char_p
-    L.igw_render_pov.argtypes = [vp, vp, vp, i32, vp, i32, vp, i32, i32, i32, vp]
-    L.igw_render_pov.restype = C.c_int
-    i64 = C.c_int64
-    L.igw_render_episodes.argtypes = [vp, i64, vp, vp, vp, vp, vp, i32, i32, vp, i32, vp, i64, i32, i32, i32, vp]
-    L.igw_render_episodes.restype = C.c_int
-    L.igw_render_views.argtypes = [vp, i64, i32, vp, vp, i32, vp, i32, vp, i32, i32, i32, vp]
-    L.igw_render_views.restype = C.c_int
+    for name, (res, args) in SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = res, args
     _lib = L
     return L
 
@@ -134,6 +80,12 @@ def check(code, what='igw_render_pov'):
     if code != 0:
         msg = load().igw_render_last_error()
         raise RenderError(f'{what} failed ({code}): {msg.decode() if msg else ""}')
+
+
+def need_device(what):
+    import torch
+    if not torch.cuda.is_available():
+        raise RenderError(f'{what} needs a HIP device (the renderer has no CPU fallback)')
 
 
 # ---- atlases ----------------------------------------------------------------------------------------------------
@@ -178,34 +130,64 @@ def load_atlas(path):
         return check_atlas(np.asarray(im.convert('RGBA'), dtype=np.uint8))
 
 
+def device_atlas(atlas, dev):
+    """The atlas a launch reads: a contiguous uint8 [S, S, 4] tensor on `dev` (S as for check_atlas) from a numpy array,
+    a CPU tensor, a tensor on `dev` (used in place) or None (the default atlas)."""
+    import torch
+    if torch.is_tensor(atlas) and atlas.device == dev:
+        if atlas.dtype != torch.uint8 or atlas.dim() != 3 or atlas.shape[2] != 4 or atlas.shape[0] != atlas.shape[1] \
+                or atlas.shape[0] % 8 or not 8 <= atlas.shape[0] <= MAX_ATLAS:
+            raise ValueError(f'an atlas is uint8 [S, S, 4], S a multiple of 8 in 8..{MAX_ATLAS}, got '
+                             f'{atlas.dtype} {tuple(atlas.shape)}')
+        return atlas.contiguous()
+    a = default_atlas() if atlas is None else check_atlas(atlas.cpu().numpy() if torch.is_tensor(atlas) else atlas)
+    return torch.from_numpy(a).to(dev)
+
+
 # ---- rendering ----------------------------------------------------------------------------------------------------
+def frame_tensor(n, size, channels, out, dev, stream=None):
+    """The frames of one launch, (out, W, H): checks `size` = (W, H) and `channels`, then allocates (on `stream`, when
+    one is given) or validates `out`, a contiguous uint8 tensor [n, H, W, channels] on `dev`."""
+    import torch
+    if channels not in (3, 4):
+        raise ValueError(f'channels must be 3 or 4, got {channels}')
+    W, H = int(size[0]), int(size[1])
+    if not (1 <= W <= MAX_SIDE and 1 <= H <= MAX_SIDE):
+        raise ValueError(f'size must be within 1..{MAX_SIDE} each way, got {size}')
+    shape = (n, H, W, channels)
+    if out is None:
+        with torch.cuda.stream(stream):
+            out = torch.empty(shape, dtype=torch.uint8, device=dev)
+    elif (not torch.is_tensor(out) or tuple(out.shape) != shape or out.dtype != torch.uint8
+          or not out.is_contiguous() or out.device != dev):
+        raise ValueError(f'out must be a contiguous uint8 tensor {shape} on {dev}')
+    return out, W, H
+
+
+def _call(entry, *args):
+    rc = getattr(load(), entry)(*args)
+    if rc:
+        check(rc, entry)
+
+
 def render_into(agent, grid, occ, n, atlas, out, width, height, channels, stream):
     """One igw_render_pov call on raw pointers (ints); `atlas` is a device tensor [S, S, 4]."""
-    L = load()
-    rc = L.igw_render_pov(agent, grid, occ, int(n), atlas.data_ptr(), int(atlas.shape[0]), out, int(width),
-                          int(height), int(channels), stream)
-    if rc:
-        check(rc)
+    _call('igw_render_pov', agent, grid, occ, int(n), atlas.data_ptr(), int(atlas.shape[0]), out, int(width),
+          int(height), int(channels), stream)
 
 
 def render_episodes_into(records, n_records, first, length, frame0, start_grid, init_pose, m, max_length, atlas, out,
                          n_frames, width, height, channels, stream):
     """One igw_render_episodes call on raw pointers (ints); `atlas` is a device tensor [S, S, 4]."""
-    L = load()
-    rc = L.igw_render_episodes(records, int(n_records), first, length, frame0, start_grid, init_pose, int(m),
-                               int(max_length), atlas.data_ptr(), int(atlas.shape[0]), out, int(n_frames), int(width),
-                               int(height), int(channels), stream)
-    if rc:
-        check(rc, 'igw_render_episodes')
+    _call('igw_render_episodes', records, int(n_records), first, length, frame0, start_grid, init_pose, int(m),
+          int(max_length), atlas.data_ptr(), int(atlas.shape[0]), out, int(n_frames), int(width), int(height),
+          int(channels), stream)
 
 
 def render_views_into(grids, grid_stride, n_grids, view_grid, pose, m, atlas, out, width, height, channels, stream):
     """One igw_render_views call on raw pointers (ints; view_grid may be None); `atlas` is a device tensor [S, S, 4]."""
-    L = load()
-    rc = L.igw_render_views(grids, int(grid_stride), int(n_grids), view_grid, pose, int(m), atlas.data_ptr(),
-                            int(atlas.shape[0]), out, int(width), int(height), int(channels), stream)
-    if rc:
-        check(rc, 'igw_render_views')
+    _call('igw_render_views', grids, int(grid_stride), int(n_grids), view_grid, pose, int(m), atlas.data_ptr(),
+          int(atlas.shape[0]), out, int(width), int(height), int(channels), stream)
 
 
 if __name__ == '__main__':

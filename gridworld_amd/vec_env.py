@@ -400,13 +400,11 @@ class VecGridWorld:
         of 8 up to 256 -- e.g. render.load_atlas('texture.png') of the reference for its look.  Default: the flat-colour
         atlas of render.default_atlas()."""
         from . import render as R
-        a = R.check_atlas(atlas.cpu().numpy() if torch.is_tensor(atlas) else atlas)
-        self._render_atlas = torch.from_numpy(a).to(self.device)
+        self._render_atlas = R.device_atlas(atlas, self.device)
 
     def _atlas(self):
         if self._render_atlas is None:
-            from . import render as R
-            self._render_atlas = torch.from_numpy(R.default_atlas()).to(self.device)
+            self.set_render_atlas(None)
         return self._render_atlas
 
     def render_pov(self, out=None, channels=3, size=None):
@@ -776,20 +774,7 @@ class SubBatch:
 def _render_rows(env, agent, grid, occ, n, out, channels, size, stream, stream_obj=None):
     """igw_render_pov over rows of a batch's state buffers (a whole VecGridWorld or a SubBatch's slice)."""
     from . import render as R
-    if channels not in (3, 4):
-        raise ValueError(f'channels must be 3 or 4, got {channels}')
-    W, H = (int(size[0]), int(size[1])) if size is not None else env.render_size
-    shape = (n, H, W, channels)
-    if out is None:
-        if stream_obj is not None:
-            with torch.cuda.stream(stream_obj):
-                out = torch.empty(shape, dtype=torch.uint8, device=env.device)
-        else:
-            out = torch.empty(shape, dtype=torch.uint8, device=env.device)
-    elif (tuple(out.shape) != shape or out.dtype != torch.uint8 or not out.is_contiguous()
-          or out.device != env.device):
-        raise ValueError(f'out must be a contiguous uint8 tensor {shape} on {env.device}, got '
-                         f'{out.dtype} {tuple(out.shape)} on {out.device}')
+    out, W, H = R.frame_tensor(n, size if size is not None else env.render_size, channels, out, env.device, stream_obj)
     R.render_into(agent.data_ptr(), grid.data_ptr(), occ.data_ptr(), n, env._atlas(), out.data_ptr(), W, H, channels,
                   stream)
     return out

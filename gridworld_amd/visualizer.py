@@ -84,18 +84,6 @@ def _grid_rows(grids, dev):
     return t, stride, n
 
 
-def _device_atlas(atlas, dev):
-    import torch
-    if torch.is_tensor(atlas) and atlas.device == dev:
-        if atlas.dtype != torch.uint8 or atlas.dim() != 3 or atlas.shape[2] != 4 or atlas.shape[0] != atlas.shape[1] \
-                or atlas.shape[0] % 8 or not 8 <= atlas.shape[0] <= R.MAX_ATLAS:
-            raise ValueError(f'an atlas is uint8 [S, S, 4], S a multiple of 8 in 8..{R.MAX_ATLAS}, got '
-                             f'{atlas.dtype} {tuple(atlas.shape)}')
-        return atlas.contiguous()
-    a = R.default_atlas() if atlas is None else R.check_atlas(atlas.cpu().numpy() if torch.is_tensor(atlas) else atlas)
-    return torch.from_numpy(a).to(dev)
-
-
 def render_views(grids, poses, view_grid=None, size=(64, 64), channels=3, atlas=None, out=None, device='cuda:0'):
     """M views in one launch on the current stream: view v shows grids[view_grid[v]] (grids[v] without view_grid) from
     poses[v].  Returns a uint8 device tensor [M, H, W, channels] with W, H = size, row 0 the top image row.
@@ -110,16 +98,10 @@ def render_views(grids, poses, view_grid=None, size=(64, 64), channels=3, atlas=
       out        a contiguous uint8 tensor [M, H, W, channels] on `device` to write into (returned)
     """
     import torch
-    if not torch.cuda.is_available():
-        raise R.RenderError('render_views needs a HIP device (the renderer has no CPU fallback)')
+    R.need_device('render_views')
     dev = torch.device(device)
     if dev.type == 'cuda' and dev.index is None:
         dev = torch.device('cuda', torch.cuda.current_device())
-    if channels not in (3, 4):
-        raise ValueError(f'channels must be 3 or 4, got {channels}')
-    W, H = int(size[0]), int(size[1])
-    if not (1 <= W <= R.MAX_SIDE and 1 <= H <= R.MAX_SIDE):
-        raise ValueError(f'size must be within 1..{R.MAX_SIDE} each way, got {size}')
     g, stride, n_grids = _grid_rows(grids, dev)
     if torch.is_tensor(poses):
         p = poses.to(device=dev, dtype=torch.float64)
@@ -144,13 +126,8 @@ def render_views(grids, poses, view_grid=None, size=(64, 64), channels=3, atlas=
         if m and (idx.min() < 0 or idx.max() >= n_grids):
             raise ValueError(f'view_grid must index the {n_grids} grids, got {int(idx.min())}..{int(idx.max())}')
         vg = torch.from_numpy(idx.astype(np.int32)).to(dev)
-    shape = (m, H, W, channels)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.uint8, device=dev)
-    elif (not torch.is_tensor(out) or tuple(out.shape) != shape or out.dtype != torch.uint8
-          or not out.is_contiguous() or out.device != dev):
-        raise ValueError(f'out must be a contiguous uint8 tensor {shape} on {dev}')
-    a = _device_atlas(atlas, dev)
+    out, W, H = R.frame_tensor(m, size, channels, out, dev)
+    a = R.device_atlas(atlas, dev)
     with torch.cuda.device(dev):
         R.render_views_into(g.data_ptr(), stride, n_grids, None if vg is None else vg.data_ptr(), p.data_ptr(), m, a,
                             out.data_ptr(), W, H, channels, torch.cuda.current_stream(dev).cuda_stream)
@@ -259,11 +236,9 @@ class Visualizer:
     # -- frames --
     def _atlas(self):
         import torch
-        if not torch.cuda.is_available():
-            raise R.RenderError('Visualizer.render needs a HIP device (the renderer has no CPU fallback)')
+        R.need_device('Visualizer.render')
         if self._atlas_dev is None:
-            a = R.default_atlas() if self.atlas is None else self.atlas
-            self._atlas_dev = torch.from_numpy(a).to(self.device)
+            self._atlas_dev = R.device_atlas(self.atlas, torch.device(self.device))
         return self._atlas_dev
 
     def render(self, position=None, rotation=None, blocks=None):

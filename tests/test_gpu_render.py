@@ -3,20 +3,16 @@
 boundary band (1e-3 texel, 1e-4 world units) matches exactly; mismatches inside the band stay <= 0.1 % of the pixels
 compared.  Each test prints its mismatch counts.  All of these together are budgeted at <= 60 s."""
 import os
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
 
 import pov_model as M
 from gridworld_amd import render as R
+from render_checks import Tally, _models, _ref_atlas
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-def _ref_atlas():
-    return np.load(os.path.join(HERE, 'golden', 'texture_atlas.npz'))['atlas']
 
 
 def _state(env, rows=None):
@@ -28,28 +24,6 @@ def _state(env, rows=None):
     if rows is not None:
         a, g = a[rows], g[rows]
     return M.pose_of_agent(a), g
-
-
-def _models(poses, grids, W, H, atlas):
-    with ThreadPoolExecutor(8) as ex:
-        return list(ex.map(lambda k: M.render(poses[k], grids[k], atlas, W, H, 4), range(len(poses))))
-
-
-class Tally:
-    def __init__(self, what):
-        self.what, self.clean_bad, self.band_bad, self.n = what, 0, 0, 0
-
-    def add(self, frame, res, channels):
-        r = dict(res, image=res['image'][..., :channels])
-        c, b, n = M.compare(frame, r)
-        self.clean_bad += c
-        self.band_bad += b
-        self.n += n
-
-    def check(self):
-        print(f'{self.what}: {self.n} pixels, {self.clean_bad} mismatches outside the band, {self.band_bad} inside')
-        assert self.clean_bad == 0
-        assert self.band_bad <= 1e-3 * self.n
 
 
 def _scripted():

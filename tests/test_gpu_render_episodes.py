@@ -4,21 +4,17 @@ renderer, against igw_render_pov on the decoded log, and against the brute-force
 units; each comparison prints its mismatch counts.  All of these together are budgeted at <= 60 s."""
 import glob
 import os
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
 
 import pov_model as M
 from gridworld_amd import render as R
+from render_checks import Tally, _models, _ref_atlas
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 SPACES = ('walking', 'flying', 'walking_dict')
-
-
-def _ref_atlas():
-    return np.load(os.path.join(HERE, 'golden', 'texture_atlas.npz'))['atlas']
 
 
 def _tasks(n, seed):
@@ -128,27 +124,6 @@ def _log_poses(ep):
     return np.stack([ap[:, 0], ap[:, 1], ap[:, 2], ap[:, 4], ap[:, 3]], 1)
 
 
-class Tally:
-    def __init__(self, what):
-        self.what, self.clean_bad, self.band_bad, self.n = what, 0, 0, 0
-
-    def add(self, frame, res):
-        c, b, n = M.compare(frame, dict(res, image=res['image'][..., :3]))
-        self.clean_bad += c
-        self.band_bad += b
-        self.n += n
-
-    def check(self):
-        print(f'{self.what}: {self.n} pixels, {self.clean_bad} mismatches outside the band, {self.band_bad} inside')
-        assert self.clean_bad == 0
-        assert self.band_bad <= 1e-3 * self.n
-
-
-def _models(poses, grids, atlas):
-    with ThreadPoolExecutor(8) as ex:
-        return list(ex.map(lambda k: M.render(poses[k], grids[k], atlas, 64, 64, 4), range(len(poses))))
-
-
 @pytest.mark.parametrize('space', SPACES)
 def test_log_frames_entry0_exact_entries_exact_and_against_the_model(space):
     atlas = _ref_atlas()
@@ -167,8 +142,8 @@ def test_log_frames_entry0_exact_entries_exact_and_against_the_model(space):
         assert np.array_equal(ep['pov'][1:], _pov_of(ep['grid'][1:], poses, atlas))
         # and the model on (grid[t], f32 pose), every third entry
         ks = list(range(1, T + 1, 3))
-        for k, res in zip(ks, _models(poses[[k - 1 for k in ks]], ep['grid'][ks].astype(np.int8), atlas)):
-            tally.add(ep['pov'][k], res)
+        for k, res in zip(ks, _models(poses[[k - 1 for k in ks]], ep['grid'][ks].astype(np.int8), 64, 64, atlas)):
+            tally.add(ep['pov'][k], res, 3)
     tally.check()
 
 
@@ -181,9 +156,10 @@ def test_log_frames_follow_the_live_frames_and_keep_the_terminal_state_of_an_aut
     for ep in eps:
         e = ep['env']
         ks = list(range(1, 17, 2)) + [16]
-        for k, res in zip(ks, _models(_log_poses(ep)[[k - 1 for k in ks]], ep['grid'][ks].astype(np.int8), atlas)):
-            tally.add(live[k - 1][e], res)         # the live frame (f64 pose) against the model of the log's state
-            tally.add(ep['pov'][k], res)
+        for k, res in zip(ks, _models(_log_poses(ep)[[k - 1 for k in ks]], ep['grid'][ks].astype(np.int8), 64, 64,
+                                      atlas)):
+            tally.add(live[k - 1][e], res, 3)         # the live frame (f64 pose) against the model of the log's state
+            tally.add(ep['pov'][k], res, 3)
         assert np.array_equal(ep['pov'][0], pov0[e])
     tally.check()
     terminal = {e['env']: e['pov'][-1] for e in eps}
@@ -298,8 +274,8 @@ def test_facade_logged_writes_one_rgb_frame_per_entry(tmp_path):
     tally = Tally('facade Logged pov vs obs pov')
     for k, (pose, grid) in enumerate(states):
         res = M.render(pose, grid.astype(np.int8), atlas, 64, 64, 4)
-        tally.add(z['pov'][k], res)
-        tally.add(seen[k], res)
+        tally.add(z['pov'][k], res, 3)
+        tally.add(seen[k], res, 3)
     tally.check()
     # the vector facade logs no frames
     v = Logged(G.make('IGLUGridworldVector-v0', max_steps=5))

@@ -8,13 +8,13 @@ and the file prints its wall time (the model is brute force: one 512 x 512 view 
 """
 import os
 import time
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
 
 import pov_model as M
 from gridworld_amd import render as R
+from render_checks import Tally, _models, _ref_atlas
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -26,40 +26,6 @@ def _wall_time():
     t0 = time.time()
     yield
     print(f'\ntests/test_gpu_render_views.py: {time.time() - t0:.1f} s wall time')
-
-
-def _ref_atlas():
-    return np.load(os.path.join(HERE, 'golden', 'texture_atlas.npz'))['atlas']
-
-
-def _models(poses, grids, W, H, atlas):
-    with ThreadPoolExecutor(8) as ex:
-        return list(ex.map(lambda k: M.render(poses[k], grids[k], atlas, W, H, 4), range(len(poses))))
-
-
-class Tally:
-    def __init__(self, what):
-        self.what, self.clean_bad, self.band_bad, self.n, self.notes = what, 0, 0, 0, []
-
-    def add(self, frame, res, channels, tag=''):
-        r = dict(res, image=res['image'][..., :channels])
-        c, b, n = M.compare(frame, r)
-        if c:   # a finding: report the pixels with their margins
-            bad = (np.asarray(frame) != r['image']).any(-1) & M.clean(r)
-            for i, j in np.argwhere(bad)[:5]:
-                self.notes.append(f'{tag} pixel ({i}, {j}): face {r["face"][i, j]}, t {r["t"][i, j]:.4f}, texel margin '
-                                  f'{r["margin_texel"][i, j]:.3g}, world margin {r["margin_world"][i, j]:.3g}')
-        self.clean_bad += c
-        self.band_bad += b
-        self.n += n
-
-    def check(self):
-        print(f'{self.what}: {self.n} pixels, {self.clean_bad} mismatches outside the band, {self.band_bad} inside '
-              f'({100.0 * self.band_bad / max(self.n, 1):.4f} % of the pixels; the limit is 0.1 %)')
-        for note in self.notes:
-            print('  ' + note)
-        assert self.clean_bad == 0, self.notes
-        assert self.band_bad <= 1e-3 * self.n
 
 
 # ---- structures (in the style of tests/test_gpu_render.py: _scripted) --------------------------------------------

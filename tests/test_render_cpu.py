@@ -1,21 +1,19 @@
 """CPU side of the first-person frame ("First-person frames"): the brute-force model of the contract on
 analytic scenes, and the HIP renderer library as a cross-compiled artefact -- its code object, exports, argument
 checks and the missing-device error.  The GPU comparison of kernel against model is tests/test_gpu_render.py."""
-import ctypes
 import glob
 import json
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import pov_model as M
+from render_checks import _buffers, _forbidden, _kernel_gates, _kernel_notes_and_asm
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LLVM = '/opt/rocm/lib/llvm/bin'
 
 
 def _atlas():
@@ -187,33 +185,16 @@ def test_render_library_exports_its_declared_symbols_and_build_id():
 
 
 def test_render_code_object_has_no_scratch(tmp_path):
-    from gridworld_amd import render as R
-    lib = R.build()
-    tools = [os.path.join(LLVM, t) for t in ('llvm-objcopy', 'clang-offload-bundler', 'llvm-readelf', 'llvm-objdump')]
-    fat, co = str(tmp_path / 'fat.bin'), str(tmp_path / 'dev.co')
-    subprocess.check_call([tools[0], '--dump-section', '.hip_fatbin=' + fat, lib])
-    subprocess.check_call([tools[1], '--type=o', '--targets=hipv4-amdgcn-amd-amdhsa--gfx950', '--input=' + fat,
-                           '--output=' + co, '--unbundle'])
-    notes = subprocess.check_output([tools[2], '--notes', co], text=True)
-    blocks = notes.split('- .agpr_count:')[1:]
-    kern = [b for b in blocks if 'igw_render_pov_kernel' in b]
-    assert len(kern) == 1
-    val = lambda k: int(re.search(r'\.%s:\s+(\d+)' % k, kern[0]).group(1))  # noqa: E731
-    assert val('private_segment_fixed_size') == 0
-    assert val('vgpr_spill_count') == 0 and val('sgpr_spill_count') == 0
-    assert val('vgpr_count') <= 128
-    assert val('group_segment_fixed_size') <= 20 * 1024
-    asm = subprocess.check_output([tools[3], '-d', co], text=True)
-    assert not re.search(r'\bs_(buffer_)?(store|atomic)|\bs_scratch_|\bscratch_', asm)
+    notes, asm = _kernel_notes_and_asm(tmp_path)
+    _kernel_gates(notes, asm, 'igw_render_pov_kernel')
+    assert not _forbidden(asm)
 
 
 def test_render_pov_rejects_bad_arguments_and_a_missing_device():
     import torch
     from gridworld_amd import render as R
     L = R.load()
-    buf = (ctypes.c_uint8 * (1 << 16))()
-    p = ctypes.addressof(buf)
-    p16 = (p + 15) & ~15
+    buf, p16 = _buffers()
     ok = dict(agent=p16, grid=p16, occ=p16, n=1, atlas=p16, side=128, out=p16, w=64, h=64, c=3)
 
     def call(**kw):

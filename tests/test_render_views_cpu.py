@@ -2,7 +2,6 @@
 point is declared, exported and bound, checks its arguments like its siblings, reports a missing device, and its
 kernel passes the code-object gates of the pov kernel; the camera helpers and the Visualizer's world bookkeeping are
 host code and are checked here without a launch.  The GPU comparisons are tests/test_gpu_render_views.py."""
-import ctypes
 import os
 import re
 import subprocess
@@ -11,9 +10,9 @@ import numpy as np
 import pytest
 
 import pov_model as M
+from render_checks import LLVM, _buffers, _kernel_gates, _kernel_notes_and_asm
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LLVM = '/opt/rocm/lib/llvm/bin'
 
 
 def test_render_views_is_declared_exported_and_bound():
@@ -29,42 +28,12 @@ def test_render_views_is_declared_exported_and_bound():
     assert L.igw_render_version() == 1
 
 
-def _kernel_notes_and_asm(tmp_path):
-    from gridworld_amd import render as R
-    lib = R.build()
-    tools = [os.path.join(LLVM, t) for t in ('llvm-objcopy', 'clang-offload-bundler', 'llvm-readelf', 'llvm-objdump')]
-    fat, co = str(tmp_path / 'fat.bin'), str(tmp_path / 'dev.co')
-    subprocess.check_call([tools[0], '--dump-section', '.hip_fatbin=' + fat, lib])
-    subprocess.check_call([tools[1], '--type=o', '--targets=hipv4-amdgcn-amd-amdhsa--gfx950', '--input=' + fat,
-                           '--output=' + co, '--unbundle'])
-    notes = subprocess.check_output([tools[2], '--notes', co], text=True)
-    asm = subprocess.check_output([tools[3], '-d', co], text=True)
-    return notes, asm
-
-
 def test_render_views_code_object_gates(tmp_path):
     notes, asm = _kernel_notes_and_asm(tmp_path)
-    blocks = notes.split('- .agpr_count:')[1:]
-    kern = [b for b in blocks if 'igw_render_views_kernel' in b]
-    assert len(kern) == 1
+    kern, val, body = _kernel_gates(notes, asm, 'igw_render_views_kernel')
     # the siblings' tests select by their names
-    assert not [b for b in kern if 'igw_render_pov_kernel' in b or 'igw_render_episodes_kernel' in b]
-    val = lambda k: int(re.search(r'\.%s:\s+(\d+)' % k, kern[0]).group(1))  # noqa: E731
-    print('views kernel: %d VGPRs, %d SGPRs, %d B of LDS' % (val('vgpr_count'), val('sgpr_count'),
-                                                             val('group_segment_fixed_size')))
-    assert val('private_segment_fixed_size') == 0
-    assert val('vgpr_spill_count') == 0 and val('sgpr_spill_count') == 0
-    assert val('vgpr_count') <= 128
-    assert val('group_segment_fixed_size') <= 20 * 1024
-    body = re.search(r'^[0-9a-f]+ <\S*igw_render_views_kernel\S*>:\n(.*?)(?:\n\n|\Z)', asm, re.M | re.S).group(1)
+    assert 'igw_render_pov_kernel' not in kern and 'igw_render_episodes_kernel' not in kern
     assert 'global_store' in body and 'ds_or' in body       # vector stores of the frame, the LDS bitmap build
-    assert not re.search(r'\bs_(buffer_)?(store|atomic)|\bs_scratch_|\bscratch_', body)
-
-
-def _buffers():
-    buf = (ctypes.c_uint8 * (1 << 16))()
-    p16 = (ctypes.addressof(buf) + 15) & ~15
-    return buf, p16
 
 
 def test_render_views_rejects_bad_arguments_and_a_missing_device():
