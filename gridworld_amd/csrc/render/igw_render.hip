@@ -9,6 +9,7 @@
 // and grid go to LDS once per block, the camera basis is built once per block in f64 (like the pose it comes from)
 // and rounded to f32; every pixel then works in f32 relative to an integer origin next to the eye (all cell and
 // ground-quad boundaries are exact half-integers there).  Colours are staged in LDS and leave as 16-byte stores.
+// The _aux entries also write per-pixel depth, label and surface planes from the same launch (igw_render_frame.h).
 #include <stdio.h>
 
 #include "igw_render_frame.h"
@@ -18,11 +19,14 @@ namespace {
 constexpr int kAgentBytes = 64;        // include/igw.h: IGW_AGENT_BYTES
 constexpr int kTrajBytes = 64;         // include/igw.h: IGW_TRAJ_BYTES
 
-__global__ __launch_bounds__(kThreads) void igw_render_pov_kernel(const uint8_t* __restrict__ agent,
-                                                              const int8_t* __restrict__ grid,
-                                                              const uint32_t* __restrict__ occ,
-                                                              const uint32_t* __restrict__ atlas, int side,
-                                                              uint8_t* __restrict__ out, int W, int H, int C) {
+// Every kernel comes in two variants of one body: the plain one (the colour frame alone: render_frame<false>, no
+// trace of the planes in its code) and the _aux one (igw_render.h: igw_render_aux; render_frame<true>, `out` may be
+// NULL).  The body, prologue included, is a __device__ function template; the kernels only choose the variant.
+template <bool kAux>
+__device__ __forceinline__ void pov_block(const uint8_t* __restrict__ agent, const int8_t* __restrict__ grid,
+                                          const uint32_t* __restrict__ occ, Planes pl,
+                                          const uint32_t* __restrict__ atlas, int side, uint8_t* __restrict__ out,
+                                          int W, int H, int C) {
     const int tid = threadIdx.x;
     const int64_t env = blockIdx.x;
     if (tid < kGridStride / 16)
@@ -30,18 +34,35 @@ __global__ __launch_bounds__(kThreads) void igw_render_pov_kernel(const uint8_t*
     else if (tid >= 128 && tid < 128 + kOccWords / 4)
         s_occ4[tid - 128] = reinterpret_cast<const uint4*>(occ + env * kOccWords)[tid - 128];
     const double* pose = reinterpret_cast<const double*>(agent + env * kAgentBytes);
-    render_frame(pose, lds_occ(), lds_grid(), s_stage4, atlas, side, out, env, W, H, C);
+    render_frame<kAux>(pose, lds_occ(), lds_grid(), s_stage4, atlas, side, out, env, W, H, C, pl);
+}
+
+__global__ __launch_bounds__(kThreads) void igw_render_pov_kernel(const uint8_t* __restrict__ agent,
+                                                              const int8_t* __restrict__ grid,
+                                                              const uint32_t* __restrict__ occ,
+                                                              const uint32_t* __restrict__ atlas, int side,
+                                                              uint8_t* __restrict__ out, int W, int H, int C) {
+    pov_block<false>(agent, grid, occ, Planes{}, atlas, side, out, W, H, C);
+}
+
+__global__ __launch_bounds__(kThreads) void igw_aux_pov_kernel(const uint8_t* __restrict__ agent,
+                                                           const int8_t* __restrict__ grid,
+                                                           const uint32_t* __restrict__ occ, Planes pl,
+                                                           const uint32_t* __restrict__ atlas, int side,
+                                                           uint8_t* __restrict__ out, int W, int H, int C) {
+    pov_block<true>(agent, grid, occ, pl, atlas, side, out, W, H, C);
 }
 
 // Block (episode e, entry t, chunk): frame t of episode e, rebuilt from the episode log (igw_render.h:
 // igw_render_episodes).  The grid is the start grid with the last change of every cell among records 0..t-1 applied:
 // one strided pass over the records keeps, per cell, max(record << 3 | colour) in an LDS table (the staging area,
 // free until the pixels are shaded); the occupancy bitmap is then derived from the grid (build_occ).
-__global__ __launch_bounds__(kThreads) void igw_render_episodes_kernel(
+template <bool kAux>
+__device__ __forceinline__ void episodes_block(
     const uint8_t* __restrict__ records, int64_t n_records, const int64_t* __restrict__ first,
     const int32_t* __restrict__ length, const int64_t* __restrict__ frame0, const int8_t* __restrict__ start_grid,
-    const double* __restrict__ init_pose, int max_length, int64_t n_frames, const uint32_t* __restrict__ atlas,
-    int side, uint8_t* __restrict__ out, int W, int H, int C) {
+    const double* __restrict__ init_pose, int max_length, int64_t n_frames, Planes pl,
+    const uint32_t* __restrict__ atlas, int side, uint8_t* __restrict__ out, int W, int H, int C) {
     const int tid = threadIdx.x;
     const int64_t e = blockIdx.x / (unsigned)(max_length + 1);
     const int t = (int)(blockIdx.x - e * (max_length + 1));
@@ -76,16 +97,35 @@ __global__ __launch_bounds__(kThreads) void igw_render_episodes_kernel(
         if (w >= 0) s_grid[c] = (int8_t)(w & 7);
     }
     build_occ(s_grid, lds_occ());
-    render_frame(pose, lds_occ(), s_grid, s_stage4, atlas, side, out, f0 + t, W, H, C);
+    render_frame<kAux>(pose, lds_occ(), s_grid, s_stage4, atlas, side, out, f0 + t, W, H, C, pl);
+}
+
+__global__ __launch_bounds__(kThreads) void igw_render_episodes_kernel(
+    const uint8_t* __restrict__ records, int64_t n_records, const int64_t* __restrict__ first,
+    const int32_t* __restrict__ length, const int64_t* __restrict__ frame0, const int8_t* __restrict__ start_grid,
+    const double* __restrict__ init_pose, int max_length, int64_t n_frames, const uint32_t* __restrict__ atlas,
+    int side, uint8_t* __restrict__ out, int W, int H, int C) {
+    episodes_block<false>(records, n_records, first, length, frame0, start_grid, init_pose, max_length, n_frames,
+                          Planes{}, atlas, side, out, W, H, C);
+}
+
+__global__ __launch_bounds__(kThreads) void igw_aux_episodes_kernel(
+    const uint8_t* __restrict__ records, int64_t n_records, const int64_t* __restrict__ first,
+    const int32_t* __restrict__ length, const int64_t* __restrict__ frame0, const int8_t* __restrict__ start_grid,
+    const double* __restrict__ init_pose, int max_length, int64_t n_frames, Planes pl,
+    const uint32_t* __restrict__ atlas, int side, uint8_t* __restrict__ out, int W, int H, int C) {
+    episodes_block<true>(records, n_records, first, length, frame0, start_grid, init_pose, max_length, n_frames, pl,
+                         atlas, side, out, W, H, C);
 }
 
 // Block (view v, chunk): grid view_grid[v] (or v) seen from pose[v] (igw_render.h: igw_render_views).  The caller has
 // only grids, at any row stride, so the block copies the view's 1,089 cells to LDS itself (16-byte loads where the
 // rows are aligned, bytes otherwise) and derives the occupancy bitmap there (build_occ).
-__global__ __launch_bounds__(kThreads) void igw_render_views_kernel(
-    const int8_t* __restrict__ grids, int64_t grid_stride, int n_grids, const int32_t* __restrict__ view_grid,
-    const double* __restrict__ pose, const uint32_t* __restrict__ atlas, int side, uint8_t* __restrict__ out, int W,
-    int H, int C) {
+template <bool kAux>
+__device__ __forceinline__ void views_block(const int8_t* __restrict__ grids, int64_t grid_stride, int n_grids,
+                                            const int32_t* __restrict__ view_grid, const double* __restrict__ pose,
+                                            Planes pl, const uint32_t* __restrict__ atlas, int side,
+                                            uint8_t* __restrict__ out, int W, int H, int C) {
     const int tid = threadIdx.x;
     const int64_t v = blockIdx.x;
     // device-side values are not trusted: a view of a row outside the grids is not drawn
@@ -101,7 +141,21 @@ __global__ __launch_bounds__(kThreads) void igw_render_views_kernel(
         for (int c = tid; c < kCells; c += kThreads) s_grid[c] = g[c];
     }
     build_occ(s_grid, lds_occ());
-    render_frame(pose + 5 * v, lds_occ(), s_grid, s_stage4, atlas, side, out, v, W, H, C);
+    render_frame<kAux>(pose + 5 * v, lds_occ(), s_grid, s_stage4, atlas, side, out, v, W, H, C, pl);
+}
+
+__global__ __launch_bounds__(kThreads) void igw_render_views_kernel(
+    const int8_t* __restrict__ grids, int64_t grid_stride, int n_grids, const int32_t* __restrict__ view_grid,
+    const double* __restrict__ pose, const uint32_t* __restrict__ atlas, int side, uint8_t* __restrict__ out, int W,
+    int H, int C) {
+    views_block<false>(grids, grid_stride, n_grids, view_grid, pose, Planes{}, atlas, side, out, W, H, C);
+}
+
+__global__ __launch_bounds__(kThreads) void igw_aux_views_kernel(
+    const int8_t* __restrict__ grids, int64_t grid_stride, int n_grids, const int32_t* __restrict__ view_grid,
+    const double* __restrict__ pose, Planes pl, const uint32_t* __restrict__ atlas, int side,
+    uint8_t* __restrict__ out, int W, int H, int C) {
+    views_block<true>(grids, grid_stride, n_grids, view_grid, pose, pl, atlas, side, out, W, H, C);
 }
 
 thread_local char g_err[512] = "";
@@ -147,6 +201,85 @@ int launch(const char* entry, void (*kernel)(Params...), int64_t count, const ui
     return IGW_RENDER_OK;
 }
 
+// The planes of an _aux entry, read on the host at call time (aux == NULL: none).
+Planes planes_of(const igw_render_aux* aux) {
+    return aux ? Planes{aux->depth, aux->label, aux->surface} : Planes{nullptr, nullptr, nullptr};
+}
+
+// What an entry's frame and planes must satisfy (`pl` == NULL: the plain entry, whose `out` is checked with its other
+// buffers): something to write, and planes aligned for their element stores.  Returns 0 or the failure.
+int check_outputs(const char* entry, const uint8_t* out, const Planes* pl) {
+    if (!pl) return 0;
+    if (!out && !pl->depth && !pl->label && !pl->surface)
+        return fail(IGW_RENDER_ERR_INVALID, entry, "nothing to write: out and every plane are NULL");
+    if (!aligned(pl->depth, 4) || !aligned(pl->surface, 2))
+        return fail(IGW_RENDER_ERR_INVALID, entry, "depth must be 4-byte, surface 2-byte aligned");
+    return 0;
+}
+
+// The three pairs of entry points: the plain entry passes pl == NULL (its `out` is required, its kernel the plain
+// one), the _aux entry its planes (any of `out` and the planes may be NULL, but not all).
+int pov_entry(const char* entry, const void* agent, const int8_t* grid, const uint32_t* occ, int32_t n,
+              const uint8_t* atlas, int32_t atlas_side, uint8_t* out, int32_t width, int32_t height, int32_t channels,
+              const Planes* pl, void* stream) {
+    if (n < 0) return fail(IGW_RENDER_ERR_INVALID, entry, "n must be >= 0");
+    if (n > 0 && (!agent || !grid || !occ || !atlas || (!pl && !out)))
+        return fail(IGW_RENDER_ERR_INVALID, entry, "null buffer");
+    if (!aligned(agent, 8) || !aligned(grid, 16) || !aligned(occ, 16) || !aligned(atlas, 4))
+        return fail(IGW_RENDER_ERR_INVALID, entry, "agent must be 8-byte, grid and occ 16-byte, atlas 4-byte "
+                                                   "aligned");
+    if (const int rc = check_outputs(entry, out, pl)) return rc;
+    if (pl)
+        return launch(entry, igw_aux_pov_kernel, n, atlas, atlas_side, out, width, height, channels, stream,
+                      static_cast<const uint8_t*>(agent), grid, occ, *pl);
+    return launch(entry, igw_render_pov_kernel, n, atlas, atlas_side, out, width, height, channels, stream,
+                  static_cast<const uint8_t*>(agent), grid, occ);
+}
+
+int episodes_entry(const char* entry, const uint8_t* records, int64_t n_records, const int64_t* first,
+                   const int32_t* length, const int64_t* frame0, const int8_t* start_grid, const double* init_pose,
+                   int32_t m, int32_t max_length, const uint8_t* atlas, int32_t atlas_side, uint8_t* out,
+                   int64_t n_frames, int32_t width, int32_t height, int32_t channels, const Planes* pl, void* stream) {
+    if (m < 0) return fail(IGW_RENDER_ERR_INVALID, entry, "m must be >= 0");
+    if (max_length < 0 || max_length > IGW_RENDER_MAX_EPISODE)
+        return fail(IGW_RENDER_ERR_INVALID, entry, "max_length must be in 0..2^24");
+    if ((int64_t)m * (max_length + 1) > INT32_MAX)
+        return fail(IGW_RENDER_ERR_INVALID, entry, "m * (max_length + 1) must be < 2^31");
+    if (n_records < 0 || n_frames < 0)
+        return fail(IGW_RENDER_ERR_INVALID, entry, "n_records and n_frames must be >= 0");
+    if (m > 0 && (!records || !first || !length || !frame0 || !start_grid || !init_pose || !atlas || (!pl && !out)))
+        return fail(IGW_RENDER_ERR_INVALID, entry, "null buffer");
+    if (!aligned(records, 16) || !aligned(first, 8) || !aligned(length, 4) || !aligned(frame0, 8) ||
+        !aligned(start_grid, 16) || !aligned(init_pose, 8) || !aligned(atlas, 4))
+        return fail(IGW_RENDER_ERR_INVALID, entry, "records and start_grid must be 16-byte, first, frame0 and "
+                                                   "init_pose 8-byte, length and atlas 4-byte aligned");
+    if (const int rc = check_outputs(entry, out, pl)) return rc;
+    const int64_t blocks = (int64_t)m * (max_length + 1);
+    if (pl)
+        return launch(entry, igw_aux_episodes_kernel, blocks, atlas, atlas_side, out, width, height, channels, stream,
+                      records, n_records, first, length, frame0, start_grid, init_pose, (int)max_length, n_frames, *pl);
+    return launch(entry, igw_render_episodes_kernel, blocks, atlas, atlas_side, out, width, height, channels, stream,
+                  records, n_records, first, length, frame0, start_grid, init_pose, (int)max_length, n_frames);
+}
+
+int views_entry(const char* entry, const int8_t* grids, int64_t grid_stride, int32_t n_grids, const int32_t* view_grid,
+                const double* pose, int32_t m, const uint8_t* atlas, int32_t atlas_side, uint8_t* out, int32_t width,
+                int32_t height, int32_t channels, const Planes* pl, void* stream) {
+    if (m < 0 || n_grids < 0) return fail(IGW_RENDER_ERR_INVALID, entry, "m and n_grids must be >= 0");
+    if (grid_stride < kCells) return fail(IGW_RENDER_ERR_INVALID, entry, "grid_stride must be >= 1089");
+    if (!view_grid && n_grids < m)
+        return fail(IGW_RENDER_ERR_INVALID, entry, "without view_grid, view v shows row v: n_grids must be >= m");
+    if (m > 0 && (!grids || !pose || !atlas || (!pl && !out))) return fail(IGW_RENDER_ERR_INVALID, entry, "null buffer");
+    if (!aligned(view_grid, 4) || !aligned(pose, 8) || !aligned(atlas, 4))
+        return fail(IGW_RENDER_ERR_INVALID, entry, "pose must be 8-byte, view_grid and atlas 4-byte aligned");
+    if (const int rc = check_outputs(entry, out, pl)) return rc;
+    if (pl)
+        return launch(entry, igw_aux_views_kernel, m, atlas, atlas_side, out, width, height, channels, stream, grids,
+                      grid_stride, (int)n_grids, view_grid, pose, *pl);
+    return launch(entry, igw_render_views_kernel, m, atlas, atlas_side, out, width, height, channels, stream, grids,
+                  grid_stride, (int)n_grids, view_grid, pose);
+}
+
 }  // namespace
 
 #ifndef IGW_RENDER_BUILD_ID
@@ -162,50 +295,47 @@ const char* igw_render_last_error(void) { return g_err; }
 
 int igw_render_pov(const void* agent, const int8_t* grid, const uint32_t* occ, int32_t n, const uint8_t* atlas,
                    int32_t atlas_side, uint8_t* out, int32_t width, int32_t height, int32_t channels, void* stream) {
-    if (n < 0) return fail(IGW_RENDER_ERR_INVALID, __func__, "n must be >= 0");
-    if (n > 0 && (!agent || !grid || !occ || !atlas || !out))
-        return fail(IGW_RENDER_ERR_INVALID, __func__, "null buffer");
-    if (!aligned(agent, 8) || !aligned(grid, 16) || !aligned(occ, 16) || !aligned(atlas, 4))
-        return fail(IGW_RENDER_ERR_INVALID, __func__, "agent must be 8-byte, grid and occ 16-byte, atlas 4-byte "
-                                                      "aligned");
-    return launch(__func__, igw_render_pov_kernel, n, atlas, atlas_side, out, width, height, channels, stream,
-                  static_cast<const uint8_t*>(agent), grid, occ);
+    return pov_entry(__func__, agent, grid, occ, n, atlas, atlas_side, out, width, height, channels, nullptr, stream);
+}
+
+int igw_render_pov_aux(const void* agent, const int8_t* grid, const uint32_t* occ, int32_t n, const uint8_t* atlas,
+                       int32_t atlas_side, uint8_t* out, int32_t width, int32_t height, int32_t channels,
+                       const igw_render_aux* aux, void* stream) {
+    const Planes pl = planes_of(aux);
+    return pov_entry(__func__, agent, grid, occ, n, atlas, atlas_side, out, width, height, channels, &pl, stream);
 }
 
 int igw_render_episodes(const uint8_t* records, int64_t n_records, const int64_t* first, const int32_t* length,
                         const int64_t* frame0, const int8_t* start_grid, const double* init_pose, int32_t m,
                         int32_t max_length, const uint8_t* atlas, int32_t atlas_side, uint8_t* out, int64_t n_frames,
                         int32_t width, int32_t height, int32_t channels, void* stream) {
-    if (m < 0) return fail(IGW_RENDER_ERR_INVALID, __func__, "m must be >= 0");
-    if (max_length < 0 || max_length > IGW_RENDER_MAX_EPISODE)
-        return fail(IGW_RENDER_ERR_INVALID, __func__, "max_length must be in 0..2^24");
-    if ((int64_t)m * (max_length + 1) > INT32_MAX)
-        return fail(IGW_RENDER_ERR_INVALID, __func__, "m * (max_length + 1) must be < 2^31");
-    if (n_records < 0 || n_frames < 0)
-        return fail(IGW_RENDER_ERR_INVALID, __func__, "n_records and n_frames must be >= 0");
-    if (m > 0 && (!records || !first || !length || !frame0 || !start_grid || !init_pose || !atlas || !out))
-        return fail(IGW_RENDER_ERR_INVALID, __func__, "null buffer");
-    if (!aligned(records, 16) || !aligned(first, 8) || !aligned(length, 4) || !aligned(frame0, 8) ||
-        !aligned(start_grid, 16) || !aligned(init_pose, 8) || !aligned(atlas, 4))
-        return fail(IGW_RENDER_ERR_INVALID, __func__, "records and start_grid must be 16-byte, first, frame0 and "
-                                                      "init_pose 8-byte, length and atlas 4-byte aligned");
-    return launch(__func__, igw_render_episodes_kernel, (int64_t)m * (max_length + 1), atlas, atlas_side, out, width,
-                  height, channels, stream, records, n_records, first, length, frame0, start_grid, init_pose,
-                  (int)max_length, n_frames);
+    return episodes_entry(__func__, records, n_records, first, length, frame0, start_grid, init_pose, m, max_length,
+                          atlas, atlas_side, out, n_frames, width, height, channels, nullptr, stream);
+}
+
+int igw_render_episodes_aux(const uint8_t* records, int64_t n_records, const int64_t* first, const int32_t* length,
+                            const int64_t* frame0, const int8_t* start_grid, const double* init_pose, int32_t m,
+                            int32_t max_length, const uint8_t* atlas, int32_t atlas_side, uint8_t* out,
+                            int64_t n_frames, int32_t width, int32_t height, int32_t channels,
+                            const igw_render_aux* aux, void* stream) {
+    const Planes pl = planes_of(aux);
+    return episodes_entry(__func__, records, n_records, first, length, frame0, start_grid, init_pose, m, max_length,
+                          atlas, atlas_side, out, n_frames, width, height, channels, &pl, stream);
 }
 
 int igw_render_views(const int8_t* grids, int64_t grid_stride, int32_t n_grids, const int32_t* view_grid,
                      const double* pose, int32_t m, const uint8_t* atlas, int32_t atlas_side, uint8_t* out,
                      int32_t width, int32_t height, int32_t channels, void* stream) {
-    if (m < 0 || n_grids < 0) return fail(IGW_RENDER_ERR_INVALID, __func__, "m and n_grids must be >= 0");
-    if (grid_stride < kCells) return fail(IGW_RENDER_ERR_INVALID, __func__, "grid_stride must be >= 1089");
-    if (!view_grid && n_grids < m)
-        return fail(IGW_RENDER_ERR_INVALID, __func__, "without view_grid, view v shows row v: n_grids must be >= m");
-    if (m > 0 && (!grids || !pose || !atlas || !out)) return fail(IGW_RENDER_ERR_INVALID, __func__, "null buffer");
-    if (!aligned(view_grid, 4) || !aligned(pose, 8) || !aligned(atlas, 4))
-        return fail(IGW_RENDER_ERR_INVALID, __func__, "pose must be 8-byte, view_grid and atlas 4-byte aligned");
-    return launch(__func__, igw_render_views_kernel, m, atlas, atlas_side, out, width, height, channels, stream, grids,
-                  grid_stride, (int)n_grids, view_grid, pose);
+    return views_entry(__func__, grids, grid_stride, n_grids, view_grid, pose, m, atlas, atlas_side, out, width,
+                       height, channels, nullptr, stream);
+}
+
+int igw_render_views_aux(const int8_t* grids, int64_t grid_stride, int32_t n_grids, const int32_t* view_grid,
+                         const double* pose, int32_t m, const uint8_t* atlas, int32_t atlas_side, uint8_t* out,
+                         int32_t width, int32_t height, int32_t channels, const igw_render_aux* aux, void* stream) {
+    const Planes pl = planes_of(aux);
+    return views_entry(__func__, grids, grid_stride, n_grids, view_grid, pose, m, atlas, atlas_side, out, width,
+                       height, channels, &pl, stream);
 }
 
 }  // extern "C"

@@ -65,15 +65,32 @@ __device__ __forceinline__ void build_occ(const int8_t* s_grid, uint32_t* s_occ)
     }
 }
 
+// The optional per-pixel planes of the _aux entries (include/igw_render.h: igw_render_aux), handed to the kernels by
+// value: depth f32 (the ray parameter t of the visible surface, +inf for sky), label u8 (0 sky, 1..6 the block's
+// colour, 7 WHITE / 8 GREY ground), surface i16 (-1 sky, face * 1089 + cell, 6 * 1089 + ground quad).  NULL = not wanted.
+struct Planes {
+    float* depth;
+    uint8_t* label;
+    int16_t* surface;
+};
+constexpr int kGroundSpan = 37;        // ground quads per side, centres -18 .. 18
+constexpr int kLabelWhite = 7;         // label of the WHITE ground; GREY is the next one
+
 // One chunk of one frame: pixels [c0, c0 + kChunk) of frame `frame` of `out` ([*][H][W][C], c0 = blockIdx.y *
 // kChunk), seen from `pose` (x, y, z, yaw, pitch in degrees: the order of an agent record, include/igw.h) in the grid
 // and occupancy bitmap that the block is writing to LDS.  Every thread of the block calls it; its first barrier
 // publishes s_grid / s_occ, so the caller's LDS stores may still be in flight.  The colours are staged in s_stage4
 // (kChunk * 4 bytes) and leave as 16-byte stores where the alignment allows.
+// kAux = true also writes the planes of `pl` that are not NULL, from the same registers the colour is shaded from:
+// consecutive threads hold consecutive pixels, so each plane leaves as coalesced 4-, 2- and 1-byte stores.  `out`
+// may then be NULL (no texel fetch, no staging, no colour stores).  kAux = false compiles all of it away (`pl` is
+// never read and `out` is taken as given).
+template <bool kAux>
 __device__ __forceinline__ void render_frame(const double* pose, const uint32_t* s_occ, const int8_t* s_grid,
                                              uint4* s_stage4, const uint32_t* atlas, int side, uint8_t* out,
-                                             int64_t frame, int W, int H, int C) {
+                                             int64_t frame, int W, int H, int C, Planes pl = Planes{}) {
     const int tid = threadIdx.x;
+    const bool shade = !kAux || out != nullptr;
     // camera (gridworld/render.py:94-111): forward = get_sight_vector, right, up; f64 like the pose
     const double ex = pose[0], ey = pose[1], ez = pose[2];
     double sy, cy, sp, cp;
@@ -103,6 +120,8 @@ __device__ __forceinline__ void render_frame(const double* pose, const uint32_t*
         const int pix = c0 + q;
         const int i = pix / W, j = pix - (pix / W) * W;
         uint32_t rgba = IGW_RENDER_CLEAR_RGBA;
+        float depth = INFINITY;            // the planes' sky (kAux only)
+        int label = 0, surface = -1;
         if (visible) {
             // d = f + ((2j+1)/W - 1)(W/H) r + (1 - (2i+1)/H) u: t along d is the eye-space depth
             const float a = (float)(2 * j + 1 - W) * inv_h, b = (float)(H - 2 * i - 1) * inv_h;
@@ -183,8 +202,10 @@ __device__ __forceinline__ void render_frame(const double* pose, const uint32_t*
                     case kFront: u = lx; v = ly; cu = 1; cv = 1; break;
                     default: u = 1.f - lx; v = ly; cu = 1; cv = 1; break;
                 }
-                int id = s_grid[hy * 121 + hx * 11 + hz];
+                const int cell = hy * 121 + hx * 11 + hz;
+                int id = s_grid[cell];
                 id = id < 1 ? 1 : id > 6 ? 6 : id;   // BLUE .. YELLOW (world grids hold no other id)
+                if constexpr (kAux) { depth = th; label = id; surface = face * kCells + cell; }
                 const int tile = id + 1;            // tiles (2,0) (3,0) (0,1) (1,1) (2,1) (3,1), utils.py:139-146
                 col = (tile & 3) * 2 * sub + cu * sub + texel_index(u, sub);
                 rowb = (tile >> 2) * 2 * sub + cv * sub + texel_index(v, sub);
@@ -199,10 +220,21 @@ __device__ __forceinline__ void render_frame(const double* pose, const uint32_t*
                         const int tile = (qx >= -5 && qx <= 5 && qz >= -5 && qz <= 5) ? 0 : 1;   // WHITE : GREY
                         col = tile * 2 * sub + texel_index(gz - fgz, 2 * sub);   // top face: u = z, v = x
                         rowb = texel_index(gx - fgx, 2 * sub);
+                        if constexpr (kAux) {
+                            depth = t; label = kLabelWhite + tile;
+                            surface = 6 * kCells + (qx + 18) * kGroundSpan + (qz + 18);
+                        }
                     }
                 }
             }
-            if (col >= 0) rgba = atlas[(side - 1 - rowb) * side + col];   // v = 0 is the bottom image row
+            if (shade && col >= 0) rgba = atlas[(side - 1 - rowb) * side + col];   // v = 0 is the bottom image row
+        }
+        if constexpr (kAux) {
+            const int64_t at = frame * (int64_t)wh + pix;
+            if (pl.depth) pl.depth[at] = depth;
+            if (pl.label) pl.label[at] = (uint8_t)label;
+            if (pl.surface) pl.surface[at] = (int16_t)surface;
+            if (!shade) continue;
         }
         if (C == 4) {
             reinterpret_cast<uint32_t*>(stage)[q] = rgba;
@@ -212,6 +244,7 @@ __device__ __forceinline__ void render_frame(const double* pose, const uint32_t*
             stage[3 * q + 2] = (uint8_t)(rgba >> 16);
         }
     }
+    if (!shade) return;   // block-uniform
     __syncthreads();
     // the chunk's bytes are contiguous in the frame: 16-byte stores where the alignment allows
     const int nbytes = len * C;

@@ -37,6 +37,11 @@ SIGNATURES = {
     'igw_render_episodes': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _i64, _i32, _i32,
                                       _i32, _vp]),
     'igw_render_views': (C.c_int, [_vp, _i64, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp]),
+    # the siblings with planes: `const igw_render_aux* aux` in front of `stream`
+    'igw_render_pov_aux': (C.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp]),
+    'igw_render_episodes_aux': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _i64, _i32,
+                                          _i32, _i32, _vp, _vp]),
+    'igw_render_views_aux': (C.c_int, [_vp, _i64, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp]),
 }
 EXPORTS = list(SIGNATURES)
 # the library as build.py builds it: the step library's FLAGS, an id of its own (igw_render_build_id())
@@ -46,6 +51,18 @@ source_hash, built_id, is_stale = LIBRARY.source_hash, LIBRARY.built_id, LIBRARY
 
 class RenderError(RuntimeError):
     pass
+
+
+class Aux(C.Structure):
+    """igw_render_aux: the three optional planes of the _aux entries (device pointers, None = not wanted)."""
+    _fields_ = [('depth', _vp), ('label', _vp), ('surface', _vp)]
+
+
+# the outputs of a render call with `outputs=`: 'rgb' is the colour frame, the others the planes (name -> dtype name)
+OUTPUTS = ('rgb', 'depth', 'label', 'surface')
+PLANE_DTYPES = {'depth': 'float32', 'label': 'uint8', 'surface': 'int16'}
+FACES = ('top', 'bottom', 'left', 'right', 'front', 'back')   # the face codes of `surface`; 6 = the ground
+GROUND_FACE, CELLS, GROUND_SPAN = 6, 1089, 37
 
 
 def build(force=False, verbose=False):
@@ -164,6 +181,54 @@ def frame_tensor(n, size, channels, out, dev, stream=None):
     return out, W, H
 
 
+def check_outputs(outputs):
+    """The tuple of names a call asked for: each one of OUTPUTS, none twice (ValueError before any device work)."""
+    if isinstance(outputs, str):
+        outputs = (outputs,)
+    names = tuple(outputs)
+    for k in names:
+        if k not in OUTPUTS:
+            raise ValueError(f'unknown output {k!r}; the outputs are {OUTPUTS}')
+    if len(set(names)) != len(names) or not names:
+        raise ValueError(f'outputs must name at least one output and none twice, got {names}')
+    return names
+
+
+def plane_tensors(n, size, outputs, out, dev, stream=None, channels=3):
+    """The outputs of one _aux launch, (dict name -> tensor, W, H): the sibling of frame_tensor for `outputs`, a tuple
+    of names from OUTPUTS.  'rgb' is a uint8 [n, H, W, channels] frame, the planes are [n, H, W] of PLANE_DTYPES.
+    `out` is None (everything is allocated, on `stream` when one is given) or a dict of preallocated contiguous
+    tensors on `dev` holding exactly the names asked for (nothing is allocated: the call can be captured)."""
+    import torch
+    names = check_outputs(outputs)
+    if out is not None and (not isinstance(out, dict) or set(out) != set(names)):
+        raise ValueError(f'with outputs={names}, out must be a dict holding exactly these names')
+    res = {}
+    W, H = int(size[0]), int(size[1])
+    for k in names:
+        given = None if out is None else out[k]
+        if k == 'rgb':
+            res[k], W, H = frame_tensor(n, size, channels, given, dev, stream)
+            continue
+        if not (1 <= W <= MAX_SIDE and 1 <= H <= MAX_SIDE):
+            raise ValueError(f'size must be within 1..{MAX_SIDE} each way, got {size}')
+        shape, dt = (n, H, W), getattr(torch, PLANE_DTYPES[k])
+        if given is None:
+            with torch.cuda.stream(stream):
+                given = torch.empty(shape, dtype=dt, device=dev)
+        elif (not torch.is_tensor(given) or tuple(given.shape) != shape or given.dtype != dt
+              or not given.is_contiguous() or given.device != dev):
+            raise ValueError(f'out[{k!r}] must be a contiguous {PLANE_DTYPES[k]} tensor {shape} on {dev}')
+        res[k] = given
+    return res, W, H
+
+
+def aux_args(tensors):
+    """(out pointer or None, Aux) of a plane_tensors dict: what an _aux entry takes."""
+    ptr = lambda k: tensors[k].data_ptr() if k in tensors else None  # noqa: E731
+    return ptr('rgb'), Aux(ptr('depth'), ptr('label'), ptr('surface'))
+
+
 def _call(entry, *args):
     rc = getattr(load(), entry)(*args)
     if rc:
@@ -188,6 +253,82 @@ def render_views_into(grids, grid_stride, n_grids, view_grid, pose, m, atlas, ou
     """One igw_render_views call on raw pointers (ints; view_grid may be None); `atlas` is a device tensor [S, S, 4]."""
     _call('igw_render_views', grids, int(grid_stride), int(n_grids), view_grid, pose, int(m), atlas.data_ptr(),
           int(atlas.shape[0]), out, int(width), int(height), int(channels), stream)
+
+
+def render_pov_aux_into(agent, grid, occ, n, atlas, out, width, height, channels, aux, stream):
+    """One igw_render_pov_aux call: render_into's arguments (out may be None) plus `aux`, an Aux."""
+    _call('igw_render_pov_aux', agent, grid, occ, int(n), atlas.data_ptr(), int(atlas.shape[0]), out, int(width),
+          int(height), int(channels), C.byref(aux), stream)
+
+
+def render_episodes_aux_into(records, n_records, first, length, frame0, start_grid, init_pose, m, max_length, atlas,
+                             out, n_frames, width, height, channels, aux, stream):
+    """One igw_render_episodes_aux call: render_episodes_into's arguments (out may be None) plus `aux`, an Aux."""
+    _call('igw_render_episodes_aux', records, int(n_records), first, length, frame0, start_grid, init_pose, int(m),
+          int(max_length), atlas.data_ptr(), int(atlas.shape[0]), out, int(n_frames), int(width), int(height),
+          int(channels), C.byref(aux), stream)
+
+
+def render_views_aux_into(grids, grid_stride, n_grids, view_grid, pose, m, atlas, out, width, height, channels, aux,
+                          stream):
+    """One igw_render_views_aux call: render_views_into's arguments (out may be None) plus `aux`, an Aux."""
+    _call('igw_render_views_aux', grids, int(grid_stride), int(n_grids), view_grid, pose, int(m), atlas.data_ptr(),
+          int(atlas.shape[0]), out, int(width), int(height), int(channels), C.byref(aux), stream)
+
+
+# ---- reading the planes ---------------------------------------------------------------------------------------------
+def decode_surface(surface):
+    """(face, y, x, z) of a `surface` plane (tensor or numpy, any shape): the face code 0..5 (FACES) and the GRID
+    indices of the block hit (grid[y, x, z]; world x - 5, y - 1, z - 5), each -1 where the pixel is not a block (sky,
+    ground).  For the ground, surface - 6 * 1089 = (qx + 18) * 37 + (qz + 18)."""
+    import torch
+    if torch.is_tensor(surface):
+        s = surface.to(torch.int32)
+        block = (s >= 0) & (s < GROUND_FACE * CELLS)
+        div = lambda a, b: torch.div(a, b, rounding_mode='floor')  # noqa: E731
+        where = torch.where
+        minus = torch.full_like(s, -1)
+    else:
+        s = np.asarray(surface).astype(np.int32)
+        block = (s >= 0) & (s < GROUND_FACE * CELLS)
+        div = lambda a, b: a // b  # noqa: E731
+        where = np.where
+        minus = np.full_like(s, -1)
+    cell = s % CELLS
+    parts = (div(s, CELLS), div(cell, 121), div(cell, 11) % 11, cell % 11)
+    return tuple(where(block, p, minus) for p in parts)
+
+
+def unproject(depth, poses, size=None):
+    """World points [M, H, W, 3] (float64 tensor on depth's device) of a depth plane [M, H, W] seen from poses [M, 5]
+    (x, y, z, yaw, pitch in degrees): eye + depth * d with the ray d of the camera contract,
+    d = f + ((2j+1)/W - 1)(W/H) r + (1 - (2i+1)/H) u for pixel (row i, column j).  NaN where the depth is inf (sky).
+    `size` = (W, H), checked against the plane when given.  Pure torch: it runs wherever `depth` lives."""
+    import torch
+    d = depth if torch.is_tensor(depth) else torch.as_tensor(np.asarray(depth))
+    if d.dim() == 2:
+        d = d.unsqueeze(0)
+    if d.dim() != 3:
+        raise ValueError(f'depth must be [M, H, W], got {tuple(d.shape)}')
+    M, H, W = d.shape
+    if size is not None and (int(size[0]), int(size[1])) != (W, H):
+        raise ValueError(f'size {tuple(size)} does not match the depth plane [{M}, {H}, {W}] (size is (W, H))')
+    p = poses if torch.is_tensor(poses) else torch.as_tensor(np.asarray(poses, np.float64))
+    p = p.to(device=d.device, dtype=torch.float64).reshape(-1, 5)
+    if p.shape[0] != M:
+        raise ValueError(f'{M} depth planes but {p.shape[0]} poses')
+    yaw, pitch = torch.deg2rad(p[:, 3]), torch.deg2rad(p[:, 4])
+    sy, cy, sp, cp = torch.sin(yaw), torch.cos(yaw), torch.sin(pitch), torch.cos(pitch)
+    zero = torch.zeros_like(sy)
+    f = torch.stack([sy * cp, sp, -cy * cp], 1)
+    r = torch.stack([cy, zero, sy], 1)
+    u = torch.stack([-sy * sp, cp, cy * sp], 1)
+    a = ((2 * torch.arange(W, dtype=torch.float64, device=d.device) + 1) / W - 1) * (W / H)
+    b = 1 - (2 * torch.arange(H, dtype=torch.float64, device=d.device) + 1) / H
+    rays = f[:, None, None, :] + a[None, None, :, None] * r[:, None, None, :] + b[None, :, None, None] * u[:, None, None, :]
+    t = d.to(torch.float64)
+    pts = p[:, None, None, :3] + t[..., None] * rays
+    return torch.where(torch.isfinite(t)[..., None], pts, torch.full_like(pts, float('nan')))
 
 
 if __name__ == '__main__':

@@ -37,7 +37,7 @@ class VecGridWorld:
                  size_reward=True, max_steps=250, right_placement_scale=1., wrong_placement_scale=0.1,
                  discretize=True, autoreset=False, num_tasks=None, lanes_per_env=0, debug_flags=0, env_index_base=0,
                  host_records=False, render=False, render_size=(64, 64), target_in_obs=False, vector_state=True, name='', fake=False,
-                 renderer=None):
+                 renderer=None, pov_outputs=('rgb',)):
         """create_env's keyword arguments (gridworld/env.py:333-338) plus the batch's own: num_envs, device,
         autoreset (reset inside step), num_tasks (rows of the task table, default num_envs), lanes_per_env
         (0 = automatic), env_index_base (global index of env 0: rank / sub-batch offset), debug_flags (IGW_DIAG
@@ -48,9 +48,17 @@ class VecGridWorld:
         vector_state=True path (observations are the state tensors; `targets()` gives the target grids).
         renderer='hip' adds the reference's first-person frame: reset() / step() also return obs['pov'], a uint8
         [N, H, W, 3] device tensor (W, H = render_size) rendered by libigw_render.so on the same stream after the
-        step / reset launch, the same tensor every call (render_pov(), DESIGN.md "First-person frames")."""
+        step / reset launch, the same tensor every call (render_pov(), DESIGN.md "First-person frames").
+        pov_outputs (with renderer='hip') names what that launch writes: 'rgb' is obs['pov']; 'depth' (float32),
+        'label' (uint8) and 'surface' (int16) add obs keys of those names, persistent [N, H, W] planes rewritten by
+        every reset() / step() in the same launch (include/igw_render.h: igw_render_aux).  The default, ('rgb',), is
+        obs['pov'] alone."""
         if renderer not in (None, 'hip'):
             raise ValueError(f"unknown renderer {renderer!r}; the one renderer is 'hip'")
+        from . import render as _R
+        pov_outputs = _R.check_outputs(pov_outputs)
+        if renderer is None and pov_outputs != ('rgb',):
+            raise ValueError("pov_outputs needs renderer='hip'")
         if render and not fake and renderer is None:
             raise NotImplementedError("render=True needs renderer='hip' (the batched HIP ray caster of the "
                                       "first-person frame); or pass render=False")
@@ -117,8 +125,15 @@ class VecGridWorld:
         self.render_size = (int(render_size[0]), int(render_size[1]))
         self._render_atlas = None
         self.pov = None   # obs['pov'] of renderer='hip': [N, H, W, 3], rewritten by every reset / step
-        if renderer == 'hip':
+        # what reset / step draw (renderer='hip'): output name -> persistent tensor; None for the default ('rgb',),
+        # which goes through the plain entry into self.pov
+        self.pov_outputs = pov_outputs if renderer == 'hip' else ()
+        self._pov_planes = None
+        if renderer == 'hip' and pov_outputs == ('rgb',):
             self.pov = torch.empty((N, self.render_size[1], self.render_size[0], 3), dtype=torch.uint8, device=dev)
+        elif renderer == 'hip':
+            self._pov_planes, _, _ = _R.plane_tensors(N, self.render_size, pov_outputs, None, dev)
+            self.pov = self._pov_planes.get('rgb')
 
     def __del__(self):
         ctx = getattr(self, 'ctx', None)
@@ -310,7 +325,7 @@ class VecGridWorld:
         L.check(self.lib.igw_reset(self.ctx, None if m is None else C.c_void_p(m.data_ptr()),
                                    L.RESET_KEEP_SIZE if keep_size else 0, self._stream()), 'igw_reset')
         self._mask_keep = m
-        if self.pov is not None:
+        if self.pov_outputs:
             return self._with_pov(self.obs())
         return self.obs()
 
@@ -350,7 +365,7 @@ class VecGridWorld:
             if rc:
                 L.check(rc, 'igw_step_walking')
             self._act_keep = a
-            if self.pov is not None:
+            if self.pov_outputs:
                 return self._with_pov(self._obs.copy()), self.reward, self.done, {}
             return self._obs.copy(), self.reward, self.done, {}
         dev = self.device
@@ -385,14 +400,30 @@ class VecGridWorld:
             if rc:
                 L.check(rc, 'igw_step_flying')
             self._act_keep = (mv, cam, inv, pl)
-        if self.pov is not None:
+        if self.pov_outputs:
             return self._with_pov(self._obs.copy()), self.reward, self.done, {}
         return self._obs.copy(), self.reward, self.done, {}
 
     # ---- first-person frames (libigw_render.so, include/igw_render.h) ----
     def _with_pov(self, obs):
-        self.render_pov(out=self.pov)
-        obs['pov'] = self.pov
+        self._draw()
+        return self._pov_keys(obs)
+
+    def _draw(self, stream=None):
+        """What reset / step draw after their launch (renderer='hip'): the persistent frame, or the persistent
+        outputs of pov_outputs in one igw_render_pov_aux launch; on the current stream unless one is given."""
+        stream = self._stream() if stream is None else stream
+        if self._pov_planes is None:
+            _render_rows(self, self.agent_buf, self.grid_buf, self.occ_buf, self.num_envs, self.pov, 3, None, stream)
+        else:
+            _render_rows(self, self.agent_buf, self.grid_buf, self.occ_buf, self.num_envs, self._pov_planes, 3, None,
+                         stream, outputs=self.pov_outputs)
+
+    def _pov_keys(self, obs):
+        if self._pov_planes is None:
+            obs['pov'] = self.pov
+        else:
+            _pov_obs(obs, self._pov_planes)
         return obs
 
     def set_render_atlas(self, atlas):
@@ -407,13 +438,16 @@ class VecGridWorld:
             self.set_render_atlas(None)
         return self._render_atlas
 
-    def render_pov(self, out=None, channels=3, size=None):
+    def render_pov(self, out=None, channels=3, size=None, outputs=None):
         """The first-person frame of every env's CURRENT state (see _make_views for auto-reset envs): uint8
         [N, H, W, channels] with W, H = size (default render_size), row 0 the top image row, channels 3 (RGB) or 4 (RGBA,
         what the reference's Renderer.render() returns).  One launch on the current stream; with `out` (a contiguous
-        uint8 device tensor of that shape) nothing is allocated, so the call can be captured in a graph."""
+        uint8 device tensor of that shape) nothing is allocated, so the call can be captured in a graph.
+        outputs (a tuple of 'rgb', 'depth', 'label', 'surface') returns a dict name -> tensor instead, from one
+        igw_render_pov_aux launch: the frame and / or the [N, H, W] planes float32 depth, uint8 label, int16 surface
+        (include/igw_render.h); `out` is then a dict of preallocated tensors under those names, or None."""
         return _render_rows(self, self.agent_buf, self.grid_buf, self.occ_buf, self.num_envs, out, channels, size,
-                            self._stream())
+                            self._stream(), outputs=outputs)
 
     def render_views(self, poses, rows=None, what='grid', **kw):
         """Views of the batch from cameras of the caller's choice (visualizer.render_views): uint8 [M, H, W, channels]
@@ -422,8 +456,8 @@ class VecGridWorld:
         grid of task-table rows, `rows` = the task row of each view (the goal image; env_task maps envs to rows; the
         table's target is the one the reward counts: the task's target grid, less its starting grid if it has one).
         rows=None: view v shows row v.  One launch on the current stream, with the env's atlas and render_size unless
-        `atlas` / `size` say otherwise; `channels` and `out` as for render_pov.  It keeps no frame tensor, so it needs
-        no renderer='hip' at construction."""
+        `atlas` / `size` say otherwise; `channels`, `out` and `outputs` as for render_pov.  It keeps no frame tensor,
+        so it needs no renderer='hip' at construction."""
         from . import visualizer as V
         try:
             grids = {'grid': self.grid_buf, 'target': self.task_target, 'start': self.task_start}[what]
@@ -451,7 +485,8 @@ class VecGridWorld:
         device memory (include/igw.h), so samplers, auto-resets and the episode log advance inside the replayed graph
         exactly as they do eagerly.  What does NOT: the sampler SETTINGS and the episode-log buffers are kernel
         parameters, frozen at capture; after set_task_sampling / set_random_tasks / enable_ / disable_trajectory_log
-        replay() raises (capture again)."""
+        replay() raises (capture again).  With renderer='hip' the graph ends with the launch that draws obs['pov'] (and
+        the planes of pov_outputs) of the state after the last step: what the eager loop's last step() leaves there."""
         self._need_tasks()
         return StepGraph(self, actions, record, chains)
 
@@ -635,6 +670,8 @@ class StepGraph:
         # step against 10.9 for the single chain -- while kernels of different STREAMS do run concurrently.)
         self.subs = env.split(chains) if chains > 1 else None   # (kept alive with the graphs)
         self.graphs = [self.graph] + [torch.cuda.CUDAGraph() for _ in range(chains - 1)]
+        if env.pov_outputs:
+            env._atlas()   # (allocated before the capture)
         self.streams = [cap] + [torch.cuda.Stream(device=dev) for _ in range(chains - 1)]
         for k in range(chains):
             st = self.streams[k]
@@ -648,6 +685,8 @@ class StepGraph:
                     L.check(fn(ctx, *(p + o for p, o in zip(ptrs[t], offs)), h), 'step (capture)')
                     if record:
                         self.outs[t, lo:lo + n].copy_(env.out_buf[lo:lo + n])
+                if env.pov_outputs:   # the frame (and planes) of the state after the last step
+                    (env if chains == 1 else self.subs[k])._draw(h)
             torch.cuda.current_stream(dev).wait_stream(st)
         if record:
             f = self.outs.view(torch.float32)
@@ -679,7 +718,8 @@ class StepGraph:
                     g.replay()
             for st in self.streams:
                 cur.wait_stream(st)
-        return env._obs.copy(), env.reward, env.done, {}
+        obs = env._obs.copy()
+        return (env._pov_keys(obs) if env.pov_outputs else obs), env.reward, env.done, {}
 
 
 class SubBatch:
@@ -710,6 +750,8 @@ class SubBatch:
         self.grid = parent.grid[sl]
         self.render_size = parent.render_size
         self.pov = None if parent.pov is None else parent.pov[sl]
+        self.pov_outputs = parent.pov_outputs
+        self._pov_planes = None if parent._pov_planes is None else {k: t[sl] for k, t in parent._pov_planes.items()}
         self._inherit_sampling()
 
     def _inherit_sampling(self):
@@ -730,21 +772,39 @@ class SubBatch:
     def obs(self):
         o = {'agentPos': self.agent_pos, 'inventory': self.inventory, 'compass': self.compass.unsqueeze(1),
              'grid': self.grid}
-        if self.pov is not None:
+        if self._pov_planes is not None:
+            _pov_obs(o, self._pov_planes)
+        elif self.pov is not None:
             o['pov'] = self.pov
         return o
+
+    def _draw(self, stream=None):
+        """What reset / step draw after their launch (renderer='hip'), on this sub-batch's stream unless one is given
+        (a capture's)."""
+        if not self.pov_outputs:
+            return
+        sl = slice(self.lo, self.lo + self.num_envs)
+        p = self.parent
+        if stream is None:
+            stream = C.c_void_p(self.stream.cuda_stream)
+            for t in (self._pov_planes.values() if self._pov_planes is not None else (self.pov,)):
+                t.record_stream(self.stream)
+        out = self.pov if self._pov_planes is None else self._pov_planes
+        _render_rows(self, p.agent_buf[sl], p.grid_buf[sl], p.occ_buf[sl], self.num_envs, out, 3, None, stream,
+                     outputs=None if self._pov_planes is None else self.pov_outputs)
 
     def _atlas(self):
         return self.parent._atlas()
 
-    def render_pov(self, out=None, channels=3, size=None):
+    def render_pov(self, out=None, channels=3, size=None, outputs=None):
         """VecGridWorld.render_pov for this sub-batch's rows, on its own stream."""
         sl = slice(self.lo, self.lo + self.num_envs)
         p = self.parent
-        if out is not None:
-            out.record_stream(self.stream)
+        for t in (out.values() if isinstance(out, dict) else () if out is None else (out,)):
+            if torch.is_tensor(t):
+                t.record_stream(self.stream)
         return _render_rows(self, p.agent_buf[sl], p.grid_buf[sl], p.occ_buf[sl], self.num_envs, out, channels, size,
-                            C.c_void_p(self.stream.cuda_stream), stream_obj=self.stream)
+                            C.c_void_p(self.stream.cuda_stream), stream_obj=self.stream, outputs=outputs)
 
     def step_walking_ptr(self, actions_i32):
         """actions_i32: contiguous int32 device tensor [n]; launched on this sub-batch's stream (the tensor is
@@ -754,13 +814,11 @@ class SubBatch:
         actions_i32.record_stream(self.stream)
         L.check(self.lib.igw_step_walking(self.ctx, actions_i32.data_ptr(), C.c_void_p(self.stream.cuda_stream)),
                 'igw_step_walking')
-        if self.pov is not None:
-            self.render_pov(out=self.pov)
+        self._draw()
 
     def reset(self):
         L.check(self.lib.igw_reset(self.ctx, None, 0, C.c_void_p(self.stream.cuda_stream)), 'igw_reset')
-        if self.pov is not None:
-            self.render_pov(out=self.pov)
+        self._draw()
         return self.obs()
 
     def synchronize(self):
@@ -771,9 +829,23 @@ class SubBatch:
         torch.cuda.current_stream(self.device).wait_stream(self.stream)
 
 
-def _render_rows(env, agent, grid, occ, n, out, channels, size, stream, stream_obj=None):
-    """igw_render_pov over rows of a batch's state buffers (a whole VecGridWorld or a SubBatch's slice)."""
+def _pov_obs(obs, planes):
+    """Adds the persistent outputs of pov_outputs to an obs dict: 'rgb' as 'pov', the planes under their names."""
+    for k, t in planes.items():
+        obs['pov' if k == 'rgb' else k] = t
+
+
+def _render_rows(env, agent, grid, occ, n, out, channels, size, stream, stream_obj=None, outputs=None):
+    """igw_render_pov (outputs=None) or igw_render_pov_aux over rows of a batch's state buffers (a whole VecGridWorld
+    or a SubBatch's slice)."""
     from . import render as R
+    if outputs is not None:
+        res, W, H = R.plane_tensors(n, size if size is not None else env.render_size, outputs, out, env.device,
+                                    stream_obj, channels=channels)
+        rgb, aux = R.aux_args(res)
+        R.render_pov_aux_into(agent.data_ptr(), grid.data_ptr(), occ.data_ptr(), n, env._atlas(), rgb, W, H, channels,
+                              aux, stream)
+        return res
     out, W, H = R.frame_tensor(n, size if size is not None else env.render_size, channels, out, env.device, stream_obj)
     R.render_into(agent.data_ptr(), grid.data_ptr(), occ.data_ptr(), n, env._atlas(), out.data_ptr(), W, H, channels,
                   stream)

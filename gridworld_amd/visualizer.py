@@ -84,7 +84,8 @@ def _grid_rows(grids, dev):
     return t, stride, n
 
 
-def render_views(grids, poses, view_grid=None, size=(64, 64), channels=3, atlas=None, out=None, device='cuda:0'):
+def render_views(grids, poses, view_grid=None, size=(64, 64), channels=3, atlas=None, out=None, device='cuda:0',
+                 outputs=None):
     """M views in one launch on the current stream: view v shows grids[view_grid[v]] (grids[v] without view_grid) from
     poses[v].  Returns a uint8 device tensor [M, H, W, channels] with W, H = size, row 0 the top image row.
 
@@ -96,8 +97,14 @@ def render_views(grids, poses, view_grid=None, size=(64, 64), channels=3, atlas=
                  device tensor is handed over as it is, and a view whose entry is out of range is left undrawn.
       atlas      uint8 [S, S, 4] (render.load_atlas / default_atlas; default: the flat colours), numpy or device tensor
       out        a contiguous uint8 tensor [M, H, W, channels] on `device` to write into (returned)
+      outputs    None: the frame alone, as above.  A tuple of names from 'rgb', 'depth', 'label', 'surface': a dict
+                 name -> tensor from the one igw_render_views_aux launch (depth float32, label uint8, surface int16,
+                 each [M, H, W]; include/igw_render.h gives their values, render.decode_surface / unproject read
+                 them); `out` is then a dict of preallocated tensors under the same names, or None.
     """
     import torch
+    if outputs is not None:
+        outputs = R.check_outputs(outputs)
     R.need_device('render_views')
     dev = torch.device(device)
     if dev.type == 'cuda' and dev.index is None:
@@ -126,8 +133,15 @@ def render_views(grids, poses, view_grid=None, size=(64, 64), channels=3, atlas=
         if m and (idx.min() < 0 or idx.max() >= n_grids):
             raise ValueError(f'view_grid must index the {n_grids} grids, got {int(idx.min())}..{int(idx.max())}')
         vg = torch.from_numpy(idx.astype(np.int32)).to(dev)
-    out, W, H = R.frame_tensor(m, size, channels, out, dev)
     a = R.device_atlas(atlas, dev)
+    if outputs is not None:
+        res, W, H = R.plane_tensors(m, size, outputs, out, dev, channels=channels)
+        rgb, aux = R.aux_args(res)
+        with torch.cuda.device(dev):
+            R.render_views_aux_into(g.data_ptr(), stride, n_grids, None if vg is None else vg.data_ptr(), p.data_ptr(),
+                                    m, a, rgb, W, H, channels, aux, torch.cuda.current_stream(dev).cuda_stream)
+        return res
+    out, W, H = R.frame_tensor(m, size, channels, out, dev)
     with torch.cuda.device(dev):
         R.render_views_into(g.data_ptr(), stride, n_grids, None if vg is None else vg.data_ptr(), p.data_ptr(), m, a,
                             out.data_ptr(), W, H, channels, torch.cuda.current_stream(dev).cuda_stream)
@@ -241,26 +255,36 @@ class Visualizer:
             self._atlas_dev = R.device_atlas(self.atlas, torch.device(self.device))
         return self._atlas_dev
 
-    def render(self, position=None, rotation=None, blocks=None):
+    def render(self, position=None, rotation=None, blocks=None, outputs=None):
         """The frame of the world from the camera: numpy uint8 [H, W, 3].  position / rotation move the camera first
         (and stay); `blocks` REPLACES the world, each block (x, y, z, id) placed at (x, y - 1, z) as in the
-        reference (a list of blocks counted from the ground level 0 rather than the world's -1)."""
+        reference (a list of blocks counted from the ground level 0 rather than the world's -1).  outputs (a tuple
+        of 'rgb', 'depth', 'label', 'surface'; render_views) gives a dict name -> numpy array instead: the frame
+        and / or the [H, W] planes, e.g. surface for picking the cell under a pixel (render.decode_surface)."""
+        if outputs is not None:
+            outputs = R.check_outputs(outputs)
         self.set_agent_state(position, rotation)
         if blocks is not None:
             self.replace_world(blocks)
         out = render_views(self.grid()[None], self.pose()[None], size=self.render_size, atlas=self._atlas(),
-                           device=self.device)
+                           device=self.device, outputs=outputs)
+        if outputs is not None:
+            return {k: v[0].cpu().numpy() for k, v in out.items()}
         return out[0].cpu().numpy()
 
-    def render_batch(self, positions, rotations, blocks=None):
+    def render_batch(self, positions, rotations, blocks=None, outputs=None):
         """T frames in one launch: numpy uint8 [T, H, W, 3].  positions [T, 3], rotations [T, 2].  blocks=None: the
         current world from the T poses (one grid, T views).  Otherwise `blocks` is a list of T block lists, frame t
         showing blocks[t] the way render(blocks=) places them (y - 1); the world is left holding the last one, and
-        the camera the last pose, as after T render() calls."""
+        the camera the last pose, as after T render() calls.  outputs: as for render(), a dict of [T, ...] arrays."""
+        if outputs is not None:
+            outputs = R.check_outputs(outputs)
         poses, grids = self.batch_inputs(positions, rotations, blocks)
         view_grid = np.zeros(len(poses), np.int32) if blocks is None else None
         out = render_views(grids, poses, view_grid=view_grid, size=self.render_size, atlas=self._atlas(),
-                           device=self.device)
+                           device=self.device, outputs=outputs)
+        if outputs is not None:
+            return {k: v.cpu().numpy() for k, v in out.items()}
         return out.cpu().numpy()
 
     def batch_inputs(self, positions, rotations, blocks=None):

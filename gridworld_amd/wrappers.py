@@ -41,13 +41,18 @@ class EpisodeLogger:
     seen from agentPos[t], the f32 pose the log holds ("First-person frames").  The last entry of an
     episode that ended in an auto-reset is its terminal state, which render_pov() can no longer show.  Like `grid`,
     the frames read the episode's task row (starting grid, init pose): a set_tasks that rewrites that row between the
-    episode and collect() changes them."""
+    episode and collect() changes them.  pov_outputs (with pov=True; default ('rgb',)) names what that launch writes,
+    as for VecGridWorld: 'rgb' is `pov`; 'depth' f32, 'label' u8 and 'surface' i16 add arrays of those names,
+    [T+1, H, W] each (include/igw_render.h: igw_render_aux), from the one igw_render_episodes_aux launch."""
 
-    def __init__(self, vec, n_envs=1, path='episodes', desc='', glob_step=0, capacity=None, pov=False):
+    def __init__(self, vec, n_envs=1, path='episodes', desc='', glob_step=0, capacity=None, pov=False,
+                 pov_outputs=('rgb',)):
         import numpy as np
+        from . import render as R
         self.np = np
         self.vec, self.path, self.desc, self.glob_step = vec, path, desc, glob_step
         self.pov = bool(pov)
+        self.pov_outputs = R.check_outputs(pov_outputs)
         self.records, self.heads = vec.enable_trajectory_log(n_envs, capacity)
         self.n_envs = int(n_envs)
         self._dumped = {}  # env -> last episode number written
@@ -93,8 +98,8 @@ class EpisodeLogger:
                 'actions': actions, 'task': int(task)}
 
     def _render(self, todo):
-        """pov frames of the episodes (env, slot, task, length, episode) in one igw_render_episodes launch on the env's
-        stream: a list of uint8 [length + 1, H, W, 3] arrays."""
+        """pov frames (and planes) of the episodes (env, slot, task, length, episode) in one igw_render_episodes (or
+        _aux) launch on the env's stream: a list of dicts array name -> [length + 1, H, W, ...] array."""
         np = self.np
         import torch
         from . import render as R
@@ -112,12 +117,18 @@ class EpisodeLogger:
         pose = v.task_meta.index_select(0, rows)[:, :40].contiguous().view(torch.float64)   # [m, 5] x, y, z, yaw, pitch
         W, H = v.render_size
         n_frames = int(frame0[-1])
-        out = torch.empty((n_frames, H, W, 3), dtype=torch.uint8, device=dev)
-        R.render_episodes_into(self.records.data_ptr(), self.records.shape[0] * 2 * cap, first.data_ptr(),
-                               length_d.data_ptr(), frame0_d.data_ptr(), start.data_ptr(), pose.data_ptr(), len(todo),
-                               cap, v._atlas(), out.data_ptr(), n_frames, W, H, 3, v._stream())
-        host = out.cpu().numpy()
-        return [host[frame0[k]:frame0[k + 1]] for k in range(len(todo))]
+        args = (self.records.data_ptr(), self.records.shape[0] * 2 * cap, first.data_ptr(), length_d.data_ptr(),
+                frame0_d.data_ptr(), start.data_ptr(), pose.data_ptr(), len(todo), cap, v._atlas())
+        if self.pov_outputs == ('rgb',):
+            out = torch.empty((n_frames, H, W, 3), dtype=torch.uint8, device=dev)
+            R.render_episodes_into(*args, out.data_ptr(), n_frames, W, H, 3, v._stream())
+            res = {'rgb': out}
+        else:
+            res, _, _ = R.plane_tensors(n_frames, (W, H), self.pov_outputs, None, dev)
+            rgb, aux = R.aux_args(res)
+            R.render_episodes_aux_into(*args, rgb, n_frames, W, H, 3, aux, v._stream())
+        host = {'pov' if k == 'rgb' else k: t.cpu().numpy() for k, t in res.items()}
+        return [{k: h[frame0[i]:frame0[i + 1]] for k, h in host.items()} for i in range(len(todo))]
 
     def collect(self, dump=True):
         """Decodes (and with dump=True writes) every logged episode that finished since the last call."""
@@ -141,7 +152,7 @@ class EpisodeLogger:
             ep = self._decode(env, slot, task, length)
             ep.update(env=env, episode=episode)
             if frames is not None:
-                ep['pov'] = frames[i]
+                ep.update(frames[i])
             if dump:
                 d = f'{self.path}/step{self.glob_step}'
                 os.makedirs(d, exist_ok=True)

@@ -25,6 +25,7 @@ extern "C" {
 #endif
 
 #define IGW_RENDER_VERSION 1
+#define IGW_RENDER_HAS_AUX 1          /* the _aux entries and igw_render_aux below exist (an addition to version 1) */
 #define IGW_RENDER_MAX_SIDE 1024      /* largest frame width / height */
 #define IGW_RENDER_MAX_ATLAS 256      /* largest atlas side (texels); the side is a multiple of 8 */
 #define IGW_RENDER_CLEAR_RGBA 0xFFFFB080u  /* (128, 176, 255, 255) as little-endian RGBA bytes */
@@ -103,6 +104,49 @@ int igw_render_episodes(const uint8_t* records, int64_t n_records, const int64_t
 int igw_render_views(const int8_t* grids, int64_t grid_stride, int32_t n_grids, const int32_t* view_grid,
                      const double* pose, int32_t m, const uint8_t* atlas, int32_t atlas_side, uint8_t* out,
                      int32_t width, int32_t height, int32_t channels, void* stream);
+
+/*
+ * Planes: what the ray caster knows about a pixel beside its colour, written by the same launch that draws the frame.
+ * Each plane is [n][height][width] over the frames of its entry (row 0 = top image row), indexed like `out` with
+ * 64-bit offsets, and follows the colour's visibility contract ("First-person frames": the first face
+ * entered with 0.1 <= t <= 30, else the ground from above within +-18.5, else sky):
+ *   depth   f32  the ray parameter t of the visible surface = its eye-space depth; +inf for sky.  4-byte aligned.
+ *   label   u8   0 sky, 1..6 the block's colour BLUE..YELLOW (an id outside 1..6 as the nearer of 1 and 6, like the
+ *                colour), 7 WHITE ground, 8 GREY ground.
+ *   surface i16  sky: -1.  Block: face * 1089 + cell, face 0..5 = top, bottom, left, right, front, back (the side
+ *                the ray enters through), cell = (y+1)*121 + (x+5)*11 + (z+5) of world (x, y, z), the grid's own
+ *                index.  Ground: 6 * 1089 + (qx + 18) * 37 + (qz + 18) for the quad centred at (qx, qz).
+ *                2-byte aligned.
+ * A pose the colour path treats as seeing nothing (not finite, or beyond 1e4) gives sky in all three.
+ * Every pointer is a device pointer or NULL (plane not wanted: no store is issued for it).  The struct itself is host
+ * memory, read during the call; the kernel receives the three pointers by value.
+ */
+typedef struct igw_render_aux {
+    float* depth;
+    uint8_t* label;
+    int16_t* surface;
+} igw_render_aux;
+
+/*
+ * igw_render_pov / igw_render_episodes / igw_render_views with planes: the arguments of the sibling, plus `aux` in
+ * front of `stream` (NULL = no planes).  The frame is byte-identical to the sibling's, and the planes do not depend
+ * on whether `out` is given.  Here `out` may be NULL (planes only: no texel is fetched, no colour stored); at least
+ * one of `out` and the three planes must not be NULL (IGW_RENDER_ERR_INVALID otherwise).  The planes follow the frame
+ * indexing of their entry: env i for pov; frame0[e] + t within n_frames for episodes, entries past length[e] left
+ * unwritten; view v for views, an undrawn view left unwritten.  Everything else (checks, device-side clamps, n == 0,
+ * asynchrony) is the sibling's.
+ */
+int igw_render_pov_aux(const void* agent, const int8_t* grid, const uint32_t* occ, int32_t n, const uint8_t* atlas,
+                       int32_t atlas_side, uint8_t* out, int32_t width, int32_t height, int32_t channels,
+                       const igw_render_aux* aux, void* stream);
+int igw_render_episodes_aux(const uint8_t* records, int64_t n_records, const int64_t* first, const int32_t* length,
+                            const int64_t* frame0, const int8_t* start_grid, const double* init_pose, int32_t m,
+                            int32_t max_length, const uint8_t* atlas, int32_t atlas_side, uint8_t* out,
+                            int64_t n_frames, int32_t width, int32_t height, int32_t channels,
+                            const igw_render_aux* aux, void* stream);
+int igw_render_views_aux(const int8_t* grids, int64_t grid_stride, int32_t n_grids, const int32_t* view_grid,
+                         const double* pose, int32_t m, const uint8_t* atlas, int32_t atlas_side, uint8_t* out,
+                         int32_t width, int32_t height, int32_t channels, const igw_render_aux* aux, void* stream);
 
 #ifdef __cplusplus
 }

@@ -26,6 +26,22 @@ igw_render_pov on as many 64 x 64 frames as shape (a) as the yardstick, --repeat
 
     python tools/bench_render.py --mode views [--out profiles/r09_render_views_bench.json]
 
+--mode aux measures the planes (igw_render_*_aux: depth, label, surface; DESIGN.md section 8 "Planes"), in one
+process, as medians of --repeats runs with the min - max spread:
+
+  colour_only  the three colour-only entries: igw_render_pov at 65,536 envs x 64 x 64, igw_render_episodes on
+               --episodes x --steps logged steps, igw_render_views on shape (a)
+  aux          igw_render_pov_aux at 65,536 envs with colour and all three planes, and with the planes alone;
+               igw_render_views_aux on shape (a) with colour and planes
+
+--mode ab --lib PATH measures the three colour-only entries on the package's library and on the one at PATH,
+alternating in ONE process over the same buffers (this, parent, this, parent, ...), --repeats times each.
+
+--lib PATH measures another build of libigw_render.so (the parent commit's, say) in place of the package's: the
+colour_only part runs on any build, the aux part only where the library has the entries.
+
+    python tools/bench_render.py --mode aux [--lib parent/libigw_render.so] [--out profiles/r10_render_aux_bench.json]
+
 The VALU side of the kernel comes from a separate profiler run ("First-person frames": measured numbers).
 """
 import argparse
@@ -231,6 +247,121 @@ def bench_views(iters, warmup, repeats):
     return res
 
 
+def _views_a(dev):
+    """Shape (a) of bench_views: 4,096 grids x 8 look-at views at 64 x 64 (grids, poses, view_grid, atlas)."""
+    import gridworld_amd as G
+    from gridworld_amd import workloads
+    ring = G.orbit_poses((0.0, 1.5, 0.0), 12, 4.5, 8, phase=10)
+    grids = workloads.uniform20(4096, seed=6).to(device=dev, dtype=torch.int8).reshape(4096, 1089).contiguous()
+    poses = torch.from_numpy(np.tile(ring, (4096, 1))).to(dev)
+    view_grid = torch.arange(4096, dtype=torch.int32, device=dev).repeat_interleave(8)
+    return grids, poses, view_grid, torch.from_numpy(G.render.default_atlas()).to(dev)
+
+
+def bench_aux(iters, warmup, repeats, episodes, steps):
+    import gridworld_amd as G
+    from gridworld_amd import render as R
+    dev = torch.device('cuda', torch.cuda.current_device())
+    have_aux = hasattr(R.load(), 'igw_render_pov_aux')
+    n = 65536
+    pix = n * 4096
+
+    def timed(fn, its=iters, frames=n):
+        us = [_time(fn, its, warmup) for _ in range(repeats)]
+        med = float(np.median(us))
+        return dict(_spread(us), ms_per_launch=round(med * 1e-3, 3), frames_per_s=round(frames / (med * 1e-6), 1))
+    colour, aux = {}, {}
+    env = _batch(n)
+    rgb = torch.empty((n, 64, 64, 3), dtype=torch.uint8, device=dev)
+    colour['pov'] = dict(timed(lambda: env.render_pov(out=rgb)), envs=n, size=[64, 64], channels=3)
+    if have_aux:
+        planes = {'depth': torch.empty((n, 64, 64), dtype=torch.float32, device=dev),
+                  'label': torch.empty((n, 64, 64), dtype=torch.uint8, device=dev),
+                  'surface': torch.empty((n, 64, 64), dtype=torch.int16, device=dev)}
+        both = dict(planes, rgb=rgb)
+        aux['pov_aux_colour_and_planes'] = dict(
+            timed(lambda: env.render_pov(out=both, outputs=('rgb', 'depth', 'label', 'surface'))), envs=n,
+            plane_bytes=7 * pix, plane_store_bound_ms_at_stream_rate=round(7 * pix / HBM_STREAM * 1e3, 3))
+        aux['pov_aux_planes_only'] = dict(timed(lambda: env.render_pov(out=planes,
+                                                                         outputs=('depth', 'label', 'surface'))), envs=n)
+        for k in ('depth', 'label', 'surface'):
+            one = {k: planes[k]}
+            aux['pov_aux_' + k + '_only'] = dict(timed(lambda: env.render_pov(out=one, outputs=(k,))), envs=n)
+        del planes, both
+    del env
+    torch.cuda.empty_cache()
+    # views, shape (a)
+    grids, poses, view_grid, atlas = _views_a(dev)
+    m = poses.shape[0]
+    out = torch.empty((m, 64, 64, 3), dtype=torch.uint8, device=dev)
+    colour['views_a'] = dict(timed(lambda: G.render_views(grids, poses, view_grid=view_grid, atlas=atlas, out=out),
+                                   frames=m), views=m, size=[64, 64], channels=3)
+    if have_aux:
+        both = {'rgb': out, 'depth': torch.empty((m, 64, 64), dtype=torch.float32, device=dev),
+                'label': torch.empty((m, 64, 64), dtype=torch.uint8, device=dev),
+                'surface': torch.empty((m, 64, 64), dtype=torch.int16, device=dev)}
+        aux['views_a_aux_colour_and_planes'] = dict(
+            timed(lambda: G.render_views(grids, poses, view_grid=view_grid, atlas=atlas, out=both,
+                                         outputs=('rgb', 'depth', 'label', 'surface')), frames=m), views=m)
+        del both
+    del out, grids, poses
+    torch.cuda.empty_cache()
+    # episodes
+    env, rec, a = _logged_episodes(episodes, steps)
+    frames = episodes * (steps + 1)
+    out = torch.empty((frames, 64, 64, 3), dtype=torch.uint8, device=dev)
+    colour['episodes'] = dict(timed(_episodes_call(env, rec, a, episodes, steps, out), its=max(3, iters // 5),
+                                    frames=frames), episodes=episodes, steps=steps, frames=frames)
+    res = {'colour_only': colour}
+    if have_aux:
+        res['aux'] = aux
+    return res
+
+
+def bench_ab(iters, warmup, repeats, episodes, steps, other):
+    """The three colour-only entries on the package's library and on `other` (a CDLL of another build), ALTERNATING
+    in one process over the same buffers: this, other, this, other, ... `repeats` times each, so that whatever drifts
+    between processes or over a session falls on both alike."""
+    import gridworld_amd as G
+    from gridworld_amd import render as R
+    dev = torch.device('cuda', torch.cuda.current_device())
+    mine = R.load()
+    n = 65536
+    env = _batch(n)
+    rgb = torch.empty((n, 64, 64, 3), dtype=torch.uint8, device=dev)
+    grids, poses, view_grid, atlas = _views_a(dev)
+    vout = torch.empty((poses.shape[0], 64, 64, 3), dtype=torch.uint8, device=dev)
+    lenv, rec, a = _logged_episodes(episodes, steps)
+    eout = torch.empty((episodes * (steps + 1), 64, 64, 3), dtype=torch.uint8, device=dev)
+    calls = {'pov': (lambda: env.render_pov(out=rgb), iters),
+             'views_a': (lambda: G.render_views(grids, poses, view_grid=view_grid, atlas=atlas, out=vout), iters),
+             'episodes': (_episodes_call(lenv, rec, a, episodes, steps, eout), max(3, iters // 5))}
+    res = {}
+    for name, (fn, its) in calls.items():
+        us = {'this': [], 'parent': []}
+        for _ in range(repeats):
+            for who, lib in (('this', mine), ('parent', other)):
+                R._lib = lib
+                us[who].append(_time(fn, its, warmup))
+        R._lib = mine
+        res[name] = {who: _spread(v) for who, v in us.items()}
+        res[name]['this_median_within_parent_spread_or_faster'] = \
+            res[name]['this']['us_per_launch_median'] <= res[name]['parent']['us_per_launch_max']
+    return res
+
+
+def _use_library(path):
+    """Binds another build of libigw_render.so in place of the package's (whatever entries it has)."""
+    import ctypes
+    from gridworld_amd import render as R
+    lib = ctypes.CDLL(os.path.abspath(path))
+    for name, (res, args) in R.SIGNATURES.items():
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.restype, fn.argtypes = res, args
+    R._lib = lib
+
+
 def _git_commit():
     import subprocess
     try:
@@ -248,7 +379,8 @@ def main():
     ap.add_argument('--facade-steps', type=int, default=500)
     ap.add_argument('--skip', default='', help='comma list of parts to skip: step, facade')
     ap.add_argument('--out', default=None)
-    ap.add_argument('--mode', default='render', choices=('render', 'episodes', 'views'))
+    ap.add_argument('--mode', default='render', choices=('render', 'episodes', 'views', 'aux', 'ab'))
+    ap.add_argument('--lib', default=None, help='another build of libigw_render.so to measure instead of the package\'s')
     ap.add_argument('--repeats', type=int, default=5, help='--mode views: repeats of every measurement')
     ap.add_argument('--git-commit', default=None, help='--mode views: the commit to stamp (default: git rev-parse)')
     ap.add_argument('--episodes', type=int, default=4096)
@@ -258,11 +390,28 @@ def main():
         sys.exit('bench_render.py needs a GPU')
     from gridworld_amd import render as R, build as B
     skip = set(filter(None, a.skip.split(',')))
+    if a.mode == 'ab':
+        if not a.lib:
+            sys.exit('--mode ab needs --lib, the other build')
+        mine = R.load()
+        _use_library(a.lib)
+        other, R._lib = R._lib, mine
+        line = {'tool': 'tools/bench_render.py', 'render_build_id': R.build_id(),
+                'parent_render_build_id': other.igw_render_build_id().decode(),
+                'device': torch.cuda.get_device_name(0),
+                'colour_only_alternating': bench_ab(a.iters, a.warmup, max(1, a.repeats), a.episodes, a.steps, other)}
+        return _emit(line, a.out)
+    if a.lib:
+        _use_library(a.lib)
     line = {'tool': 'tools/bench_render.py', 'render_build_id': R.build_id(), 'step_build_id': B.source_hash(),
             'device': torch.cuda.get_device_name(0)}
     if a.mode == 'views':
         line['git_commit'] = a.git_commit or _git_commit()
         line['views'] = bench_views(a.iters, a.warmup, max(1, a.repeats))
+        return _emit(line, a.out)
+    if a.mode == 'aux':
+        line['git_commit'] = a.git_commit or _git_commit()
+        line['aux_bench'] = bench_aux(a.iters, a.warmup, max(1, a.repeats), a.episodes, a.steps)
         return _emit(line, a.out)
     if a.mode == 'episodes':
         line['episodes'] = bench_episodes(a.episodes, a.steps, a.iters, a.warmup)
