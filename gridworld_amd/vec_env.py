@@ -438,14 +438,21 @@ class VecGridWorld:
             self.set_render_atlas(None)
         return self._render_atlas
 
-    def render_pov(self, out=None, channels=3, size=None, outputs=None):
+    def render_pov(self, out=None, channels=3, size=None, outputs=None, codec=None, quality=90):
         """The first-person frame of every env's CURRENT state (see _make_views for auto-reset envs): uint8
         [N, H, W, channels] with W, H = size (default render_size), row 0 the top image row, channels 3 (RGB) or 4 (RGBA,
         what the reference's Renderer.render() returns).  One launch on the current stream; with `out` (a contiguous
         uint8 device tensor of that shape) nothing is allocated, so the call can be captured in a graph.
         outputs (a tuple of 'rgb', 'depth', 'label', 'surface') returns a dict name -> tensor instead, from one
         igw_render_pov_aux launch: the frame and / or the [N, H, W] planes float32 depth, uint8 label, int16 surface
-        (include/igw_render.h); `out` is then a dict of preallocated tensors under those names, or None."""
+        (include/igw_render.h); `out` is then a dict of preallocated tensors under those names, or None.
+        codec='jpeg' returns (buf, sizes) of codec.encode_jpeg instead: the frames are drawn, then encoded at `quality`
+        by a second launch on the same stream; `out` is then the (buf, sizes) pair to encode into, or None."""
+        from . import codec as K
+        if K.check_codec(codec, outputs):
+            frames = _render_rows(self, self.agent_buf, self.grid_buf, self.occ_buf, self.num_envs, None, channels,
+                                  size, self._stream())
+            return K.encode_jpeg(frames, quality, out=out, check_sizes=out is None)
         return _render_rows(self, self.agent_buf, self.grid_buf, self.occ_buf, self.num_envs, out, channels, size,
                             self._stream(), outputs=outputs)
 
@@ -456,8 +463,8 @@ class VecGridWorld:
         grid of task-table rows, `rows` = the task row of each view (the goal image; env_task maps envs to rows; the
         table's target is the one the reward counts: the task's target grid, less its starting grid if it has one).
         rows=None: view v shows row v.  One launch on the current stream, with the env's atlas and render_size unless
-        `atlas` / `size` say otherwise; `channels`, `out` and `outputs` as for render_pov.  It keeps no frame tensor,
-        so it needs no renderer='hip' at construction."""
+        `atlas` / `size` say otherwise; `channels`, `out`, `outputs`, `codec` and `quality` as for render_pov.  It keeps
+        no frame tensor, so it needs no renderer='hip' at construction."""
         from . import visualizer as V
         try:
             grids = {'grid': self.grid_buf, 'target': self.task_target, 'start': self.task_start}[what]
@@ -796,10 +803,20 @@ class SubBatch:
     def _atlas(self):
         return self.parent._atlas()
 
-    def render_pov(self, out=None, channels=3, size=None, outputs=None):
+    def render_pov(self, out=None, channels=3, size=None, outputs=None, codec=None, quality=90):
         """VecGridWorld.render_pov for this sub-batch's rows, on its own stream."""
         sl = slice(self.lo, self.lo + self.num_envs)
         p = self.parent
+        from . import codec as K
+        if K.check_codec(codec, outputs):
+            frames = self.render_pov(None, channels, size)
+            for t in (out or ()):
+                t.record_stream(self.stream)
+            with torch.cuda.stream(self.stream):
+                res = K.encode_jpeg(frames, quality, out=out, check_sizes=out is None)
+            for t in res:
+                t.record_stream(self.stream)
+            return res
         for t in (out.values() if isinstance(out, dict) else () if out is None else (out,)):
             if torch.is_tensor(t):
                 t.record_stream(self.stream)

@@ -85,7 +85,7 @@ def _grid_rows(grids, dev):
 
 
 def render_views(grids, poses, view_grid=None, size=(64, 64), channels=3, atlas=None, out=None, device='cuda:0',
-                 outputs=None):
+                 outputs=None, codec=None, quality=90):
     """M views in one launch on the current stream: view v shows grids[view_grid[v]] (grids[v] without view_grid) from
     poses[v].  Returns a uint8 device tensor [M, H, W, channels] with W, H = size, row 0 the top image row.
 
@@ -101,8 +101,14 @@ def render_views(grids, poses, view_grid=None, size=(64, 64), channels=3, atlas=
                  name -> tensor from the one igw_render_views_aux launch (depth float32, label uint8, surface int16,
                  each [M, H, W]; include/igw_render.h gives their values, render.decode_surface / unproject read
                  them); `out` is then a dict of preallocated tensors under the same names, or None.
+      codec      'jpeg': (buf, sizes) of codec.encode_jpeg instead of the frames, which are drawn and then encoded at
+                 `quality` by a second launch on the same stream; `out` is then the (buf, sizes) pair to encode into.
     """
     import torch
+    from . import codec as K
+    if K.check_codec(codec, outputs):
+        frames = render_views(grids, poses, view_grid, size, channels, atlas, None, device)
+        return K.encode_jpeg(frames, quality, out=out, check_sizes=out is None)
     if outputs is not None:
         outputs = R.check_outputs(outputs)
     R.need_device('render_views')
@@ -193,10 +199,11 @@ class Visualizer:
         ValueError (the reference would draw it; the ray caster is bounded by the zone);
       * removing a block that is not there is ignored (the reference raises KeyError);
       * the frame is RGB: the reference's frame without its alpha, which render() drops there too;
-      * no render_video / postproc_video (no codec here).  render_batch(positions, rotations, blocks=None) draws T
-        poses of the current world, or T (pose, block list) pairs, in ONE launch and returns [T, H, W, 3]: the frames
-        render_video would have handed to its writer, in RGB (the writer takes them flipped to BGR).
-    Without a HIP device render() and render_batch() raise render.RenderError.
+      * render_batch(positions, rotations, blocks=None) draws T poses of the current world, or T (pose, block list)
+        pairs, in ONE launch and returns [T, H, W, 3]; render_video(output, positions, rotations, blocks=None) takes
+        the same and writes them as {output}.avi, Motion-JPEG (gridworld_amd/codec.py), where the reference writes an
+        mp4 through cv2; there is no postproc_video (no ffmpeg here).
+    Without a HIP device render(), render_batch() and render_video() raise render.RenderError.
     """
 
     def __init__(self, render_size=(64, 64), device='cuda:0', atlas=None):
@@ -286,6 +293,17 @@ class Visualizer:
         if outputs is not None:
             return {k: v.cpu().numpy() for k, v in out.items()}
         return out.cpu().numpy()
+
+    def render_video(self, output, positions, rotations, blocks=None, fps=60, quality=90):
+        """The frames of render_batch(positions, rotations, blocks) as a video: ONE render launch, ONE encode launch
+        (codec.encode_jpeg at `quality`), then {output}.avi, Motion-JPEG at `fps` (codec.write_avi).  Returns the
+        path.  The camera and the world are left as after render_batch."""
+        from . import codec as K
+        poses, grids = self.batch_inputs(positions, rotations, blocks)
+        view_grid = np.zeros(len(poses), np.int32) if blocks is None else None
+        buf, sizes = render_views(grids, poses, view_grid=view_grid, size=self.render_size, atlas=self._atlas(),
+                                  device=self.device, codec='jpeg', quality=quality)
+        return K.write_avi(f'{output}.avi', K.jpeg_bytes(buf, sizes), self.render_size, fps)
 
     def batch_inputs(self, positions, rotations, blocks=None):
         """(poses [T, 5], grids [1 or T, 9, 11, 11]) that render_batch draws; updates the camera and the world."""

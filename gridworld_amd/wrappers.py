@@ -43,16 +43,27 @@ class EpisodeLogger:
     the frames read the episode's task row (starting grid, init pose): a set_tasks that rewrites that row between the
     episode and collect() changes them.  pov_outputs (with pov=True; default ('rgb',)) names what that launch writes,
     as for VecGridWorld: 'rgb' is `pov`; 'depth' f32, 'label' u8 and 'surface' i16 add arrays of those names,
-    [T+1, H, W] each (include/igw_render.h: igw_render_aux), from the one igw_render_episodes_aux launch."""
+    [T+1, H, W] each (include/igw_render.h: igw_render_aux), from the one igw_render_episodes_aux launch.
+
+    pov_codec='jpeg' (with pov=True) keeps the frames compressed: an episode carries `pov_jpeg`, a list of T+1 byte
+    strings, in place of the raw `pov` array -- the JPEG streams (quality pov_quality) of exactly
+    the frames the raw path logs, encoded on the device by ONE igw_jpeg_encode launch behind the render launch; only
+    the streams cross to the host.  The npz holds them as `pov_jpeg` (uint8, the streams end to end) and
+    `pov_jpeg_end` (int64 [T+1], where each ends).  save_video(episode, path) writes them as a Motion-JPEG AVI."""
 
     def __init__(self, vec, n_envs=1, path='episodes', desc='', glob_step=0, capacity=None, pov=False,
-                 pov_outputs=('rgb',)):
+                 pov_outputs=('rgb',), pov_codec=None, pov_quality=90):
         import numpy as np
-        from . import render as R
+        from . import codec as K, render as R
         self.np = np
         self.vec, self.path, self.desc, self.glob_step = vec, path, desc, glob_step
         self.pov = bool(pov)
         self.pov_outputs = R.check_outputs(pov_outputs)
+        self.pov_codec, self.pov_quality = K.check_codec(pov_codec), int(pov_quality)
+        if self.pov_codec and 'rgb' not in self.pov_outputs:
+            raise ValueError("pov_codec='jpeg' encodes the colour frame: pov_outputs must hold 'rgb'")
+        if not 1 <= self.pov_quality <= 100:
+            raise ValueError(f'pov_quality must be in 1..100, got {pov_quality}')
         self.records, self.heads = vec.enable_trajectory_log(n_envs, capacity)
         self.n_envs = int(n_envs)
         self._dumped = {}  # env -> last episode number written
@@ -127,8 +138,30 @@ class EpisodeLogger:
             res, _, _ = R.plane_tensors(n_frames, (W, H), self.pov_outputs, None, dev)
             rgb, aux = R.aux_args(res)
             R.render_episodes_aux_into(*args, rgb, n_frames, W, H, 3, aux, v._stream())
+        jpegs = None
+        if self.pov_codec:
+            from . import codec as K
+            jpegs = K.jpeg_bytes(*K.encode_jpeg(res.pop('rgb'), self.pov_quality))   # on v._stream(), the current one
         host = {'pov' if k == 'rgb' else k: t.cpu().numpy() for k, t in res.items()}
-        return [{k: h[frame0[i]:frame0[i + 1]] for k, h in host.items()} for i in range(len(todo))]
+        eps = [{k: h[frame0[i]:frame0[i + 1]] for k, h in host.items()} for i in range(len(todo))]
+        if jpegs is not None:
+            for i, ep in enumerate(eps):
+                ep['pov_jpeg'] = jpegs[frame0[i]:frame0[i + 1]]
+        return eps
+
+    def save_video(self, episode, path, fps=20):
+        """Writes an episode's frames (a dict collect() returned) as a Motion-JPEG AVI at `path`: its `pov_jpeg` streams
+        as they are, or its raw `pov` frames encoded first (one igw_jpeg_encode launch at pov_quality).  Returns the
+        path."""
+        from . import codec as K
+        jpegs = episode.get('pov_jpeg')
+        if jpegs is None:
+            if 'pov' not in episode:
+                raise ValueError('the episode has no frames: log with EpisodeLogger(pov=True)')
+            import torch
+            jpegs = K.jpeg_bytes(*K.encode_jpeg(torch.from_numpy(self.np.ascontiguousarray(episode['pov']))
+                                                .to(self.vec.device), self.pov_quality))
+        return K.write_avi(path, jpegs, self.vec.render_size, fps)
 
     def collect(self, dump=True):
         """Decodes (and with dump=True writes) every logged episode that finished since the last call."""
@@ -157,7 +190,10 @@ class EpisodeLogger:
                 d = f'{self.path}/step{self.glob_step}'
                 os.makedirs(d, exist_ok=True)
                 fname = f'{d}/ep_{self.desc}_{uuid.uuid4().hex[:6]}'
-                arrays = {k: v for k, v in ep.items() if k != 'actions'}
+                arrays = {k: v for k, v in ep.items() if k not in ('actions', 'pov_jpeg')}
+                if 'pov_jpeg' in ep:
+                    arrays['pov_jpeg'] = np.frombuffer(b''.join(ep['pov_jpeg']), np.uint8)
+                    arrays['pov_jpeg_end'] = np.cumsum([len(j) for j in ep['pov_jpeg']], dtype=np.int64)
                 if isinstance(ep['actions'], dict):
                     arrays.update({'action_' + k: v for k, v in ep['actions'].items()})
                 np.savez_compressed(fname + '.npz', **arrays)
@@ -177,7 +213,9 @@ class Logged(Wrapper):
     renderer='hip', not fake) the npz holds `pov` uint8 [T+1, H, W, 3], one RGB frame per entry, equal to the env's
     obs['pov'] after each step (up to f32 rounding of the logged pose, EpisodeLogger).  The reference's own list
     interleaves that RGB frame with a render() frame flipped to BGR for its cv2 video writer (wrappers.py:95-100);
-    here there is one RGB frame per entry and no video."""
+    here there is one RGB frame per entry, and the video beside the npz, {same name}.avi, is Motion-JPEG of those
+    T+1 frames in log order (EpisodeLogger.save_video; video_fps, default 20, and video_quality, default 90, are
+    attributes) where the reference writes an mp4."""
 
     def __init__(self, env):
         super().__init__(env)
@@ -185,6 +223,7 @@ class Logged(Wrapper):
         self.turned_off = True
         u = env.unwrapped
         self._log = EpisodeLogger(u._vec, 1, path='episodes', pov=u._renders())
+        self.video_fps, self.video_quality = 20, 90
 
     def turn_on(self):
         self.turned_off = False
@@ -199,5 +238,8 @@ class Logged(Wrapper):
     def step(self, action):
         obs, reward, done, info = self.env.step(action)
         if done:
-            self._log.collect(dump=self.logging)
+            for ep in self._log.collect(dump=self.logging):
+                if 'file' in ep and 'pov' in ep:
+                    self._log.pov_quality = self.video_quality
+                    self._log.save_video(ep, ep['file'][:-4] + '.avi', self.video_fps)
         return obs, reward, done, info
