@@ -6,6 +6,7 @@
 hipcc cross-compiles without a GPU.  -ffp-contract=off is REQUIRED: the reference computes
 in IEEE binary64 with one rounding per operation; never add fast-math flags.
 """
+import ctypes
 import os
 import shutil
 import subprocess
@@ -116,6 +117,40 @@ class Library:
         except Exception as e:
             if not os.path.exists(self.lib):
                 raise error(f'{name} is missing and could not be built: {e}') from e
+
+
+class Binding:
+    """The ctypes side of a Library: load() types every symbol of `signatures` (name -> (result, arguments)), check()
+    turns a nonzero return code into `error` with the text of the `last_error` symbol, build_id() calls the
+    `build_id` symbol.  `module` is what the "not found" message says to run; `what` is check()'s default entry."""
+
+    def __init__(self, library, signatures, error, last_error, build_id, module, what):
+        self.library, self.signatures, self.error, self.module, self.what = library, signatures, error, module, what
+        self._last_error, self._build_id = last_error, build_id
+        self.lib = None
+
+    def load(self, build_if_missing=True):
+        """Loads the library, building it first if it is missing or stale; a failed compile raises."""
+        if self.lib is not None:
+            return self.lib
+        if build_if_missing:
+            self.library.build_for_load(self.error)
+        if not os.path.exists(self.library.lib):
+            raise self.error(f'{os.path.basename(self.library.lib)} not found; run `python -m {self.module}`')
+        lib = ctypes.CDLL(self.library.lib)
+        for name, (res, args) in self.signatures.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = res, args
+        self.lib = lib
+        return lib
+
+    def build_id(self):
+        return getattr(self.load(), self._build_id)().decode()
+
+    def check(self, code, what=None):
+        if code != 0:
+            msg = getattr(self.load(), self._last_error)()
+            raise self.error(f'{what or self.what} failed ({code}): {msg.decode() if msg else ""}')
 
 
 # The step library and its diagnostic variant (libigw_hip_diag.so, -DIGW_DIAG, next to the production library).  The

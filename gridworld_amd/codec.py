@@ -50,34 +50,9 @@ def build(force=False, verbose=False):
     return LIBRARY.build(force, verbose=verbose)
 
 
-_lib = None
-
-
-def load(build_if_missing=True):
-    """Loads libigw_codec.so, building it first if it is missing or stale; a failed compile raises."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if build_if_missing:
-        LIBRARY.build_for_load(CodecError)
-    if not os.path.exists(LIB):
-        raise CodecError('libigw_codec.so not found; run `python -m gridworld_amd.codec`')
-    L = C.CDLL(LIB)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(L, name)
-        fn.restype, fn.argtypes = res, args
-    _lib = L
-    return L
-
-
-def build_id():
-    return load().igw_codec_build_id().decode()
-
-
-def check(code, what='igw_jpeg_encode'):
-    if code != 0:
-        msg = load().igw_codec_last_error()
-        raise CodecError(f'{what} failed ({code}): {msg.decode() if msg else ""}')
+BINDING = _build.Binding(LIBRARY, SIGNATURES, CodecError, 'igw_codec_last_error', 'igw_codec_build_id',
+                         'gridworld_amd.codec', 'igw_jpeg_encode')
+load, check, build_id = BINDING.load, BINDING.check, BINDING.build_id
 
 
 def jpeg_bound(width, height):
@@ -167,9 +142,18 @@ def check_codec(codec, outputs=None):
         return None
     if codec != 'jpeg':
         raise ValueError(f"codec must be None or 'jpeg', got {codec!r}")
-    if outputs is not None:
-        raise ValueError("codec='jpeg' encodes the colour frame: it cannot be combined with outputs=")
-    return codec
+    if outputs is None:
+        return codec
+    raise ValueError("codec='jpeg' encodes the colour frame: it cannot be combined with outputs=")
+
+
+def encoded(codec, outputs, quality, out, draw):
+    """The "draw, then encode" step of a render call that takes `codec`: None without a codec (the caller draws what
+    it was asked for); with one, (buf, sizes) of the raw frames `draw()` returns, encoded by a second launch on the
+    current stream into `out`, the (buf, sizes) pair to write into, or into fresh tensors that are grown to fit."""
+    if not check_codec(codec, outputs):
+        return None
+    return encode_jpeg(draw(), quality, out=out, check_sizes=out is None)
 
 
 def jpeg_bytes(buf, sizes):

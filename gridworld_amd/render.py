@@ -37,12 +37,10 @@ SIGNATURES = {
     'igw_render_episodes': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _i64, _i32, _i32,
                                       _i32, _vp]),
     'igw_render_views': (C.c_int, [_vp, _i64, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp]),
-    # the siblings with planes: `const igw_render_aux* aux` in front of `stream`
-    'igw_render_pov_aux': (C.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp]),
-    'igw_render_episodes_aux': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _i64, _i32,
-                                          _i32, _i32, _vp, _vp]),
-    'igw_render_views_aux': (C.c_int, [_vp, _i64, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp]),
 }
+# the siblings with planes: `const igw_render_aux* aux` in front of `stream`
+SIGNATURES.update({name + '_aux': (res, args[:-1] + [_vp] + args[-1:])
+                   for name, (res, args) in list(SIGNATURES.items()) if args})
 EXPORTS = list(SIGNATURES)
 # the library as build.py builds it: the step library's FLAGS, an id of its own (igw_render_build_id())
 LIBRARY = _build.Library(LIB, SOURCES, HEADERS, 'igw-render-build-id:', 'IGW_RENDER_BUILD_ID', deps=[__file__])
@@ -69,34 +67,9 @@ def build(force=False, verbose=False):
     return LIBRARY.build(force, verbose=verbose)
 
 
-_lib = None
-
-
-def load(build_if_missing=True):
-    """Loads libigw_render.so, building it first if it is missing or stale; a failed compile raises."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if build_if_missing:
-        LIBRARY.build_for_load(RenderError)
-    if not os.path.exists(LIB):
-        raise RenderError('libigw_render.so not found; run `python -m gridworld_amd.render`')
-    L = C.CDLL(LIB)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(L, name)
-        fn.restype, fn.argtypes = res, args
-    _lib = L
-    return L
-
-
-def build_id():
-    return load().igw_render_build_id().decode()
-
-
-def check(code, what='igw_render_pov'):
-    if code != 0:
-        msg = load().igw_render_last_error()
-        raise RenderError(f'{what} failed ({code}): {msg.decode() if msg else ""}')
+BINDING = _build.Binding(LIBRARY, SIGNATURES, RenderError, 'igw_render_last_error', 'igw_render_build_id',
+                         'gridworld_amd.render', 'igw_render_pov')
+load, check, build_id = BINDING.load, BINDING.check, BINDING.build_id
 
 
 def need_device(what):
@@ -162,27 +135,11 @@ def device_atlas(atlas, dev):
 
 
 # ---- rendering ----------------------------------------------------------------------------------------------------
-def frame_tensor(n, size, channels, out, dev, stream=None):
-    """The frames of one launch, (out, W, H): checks `size` = (W, H) and `channels`, then allocates (on `stream`, when
-    one is given) or validates `out`, a contiguous uint8 tensor [n, H, W, channels] on `dev`."""
-    import torch
-    if channels not in (3, 4):
-        raise ValueError(f'channels must be 3 or 4, got {channels}')
-    W, H = int(size[0]), int(size[1])
-    if not (1 <= W <= MAX_SIDE and 1 <= H <= MAX_SIDE):
-        raise ValueError(f'size must be within 1..{MAX_SIDE} each way, got {size}')
-    shape = (n, H, W, channels)
-    if out is None:
-        with torch.cuda.stream(stream):
-            out = torch.empty(shape, dtype=torch.uint8, device=dev)
-    elif (not torch.is_tensor(out) or tuple(out.shape) != shape or out.dtype != torch.uint8
-          or not out.is_contiguous() or out.device != dev):
-        raise ValueError(f'out must be a contiguous uint8 tensor {shape} on {dev}')
-    return out, W, H
-
-
 def check_outputs(outputs):
-    """The tuple of names a call asked for: each one of OUTPUTS, none twice (ValueError before any device work)."""
+    """The `outputs` argument of a render call: None (the colour frame alone) as it is, otherwise the tuple of names
+    asked for, each one of OUTPUTS, none twice (ValueError before any device work)."""
+    if outputs is None:
+        return None
     if isinstance(outputs, str):
         outputs = (outputs,)
     names = tuple(outputs)
@@ -194,86 +151,95 @@ def check_outputs(outputs):
     return names
 
 
-def plane_tensors(n, size, outputs, out, dev, stream=None, channels=3):
-    """The outputs of one _aux launch, (dict name -> tensor, W, H): the sibling of frame_tensor for `outputs`, a tuple
-    of names from OUTPUTS.  'rgb' is a uint8 [n, H, W, channels] frame, the planes are [n, H, W] of PLANE_DTYPES.
-    `out` is None (everything is allocated, on `stream` when one is given) or a dict of preallocated contiguous
-    tensors on `dev` holding exactly the names asked for (nothing is allocated: the call can be captured)."""
+def _tensor(shape, dtype, given, dev, stream, name):
+    """One tensor of a launch: allocated (on `stream`, when one is given) or `given`, validated: a contiguous tensor of
+    that shape and dtype (a torch dtype's name) on `dev`; `name` is what the error message calls it."""
     import torch
+    dt = getattr(torch, dtype)
+    if given is None:
+        with torch.cuda.stream(stream):
+            return torch.empty(shape, dtype=dt, device=dev)
+    if (not torch.is_tensor(given) or tuple(given.shape) != shape or given.dtype != dt or not given.is_contiguous()
+            or given.device != dev):
+        raise ValueError(f'{name} must be a contiguous {dtype} tensor {shape} on {dev}')
+    return given
+
+
+def targets(n, size, channels, outputs, out, dev, stream=None):
+    """What one launch of n frames writes, (tensors, W, H), after checking `size` = (W, H) and `channels`.
+    outputs=None: the uint8 [n, H, W, channels] frame, `out` or a new one.  A tuple of names from OUTPUTS: a dict
+    name -> tensor, 'rgb' that frame and the planes [n, H, W] of PLANE_DTYPES; `out` is then None or a dict of
+    preallocated tensors holding exactly the names asked for.  With `out` nothing is allocated (the call can be
+    captured); what is allocated is allocated on `stream`, when one is given."""
+    if channels not in (3, 4):
+        raise ValueError(f'channels must be 3 or 4, got {channels}')
+    W, H = int(size[0]), int(size[1])
+    if not (1 <= W <= MAX_SIDE and 1 <= H <= MAX_SIDE):
+        raise ValueError(f'size must be within 1..{MAX_SIDE} each way, got {size}')
+    if outputs is None:
+        return _tensor((n, H, W, channels), 'uint8', out, dev, stream, 'out'), W, H
     names = check_outputs(outputs)
     if out is not None and (not isinstance(out, dict) or set(out) != set(names)):
         raise ValueError(f'with outputs={names}, out must be a dict holding exactly these names')
     res = {}
-    W, H = int(size[0]), int(size[1])
     for k in names:
-        given = None if out is None else out[k]
-        if k == 'rgb':
-            res[k], W, H = frame_tensor(n, size, channels, given, dev, stream)
-            continue
-        if not (1 <= W <= MAX_SIDE and 1 <= H <= MAX_SIDE):
-            raise ValueError(f'size must be within 1..{MAX_SIDE} each way, got {size}')
-        shape, dt = (n, H, W), getattr(torch, PLANE_DTYPES[k])
-        if given is None:
-            with torch.cuda.stream(stream):
-                given = torch.empty(shape, dtype=dt, device=dev)
-        elif (not torch.is_tensor(given) or tuple(given.shape) != shape or given.dtype != dt
-              or not given.is_contiguous() or given.device != dev):
-            raise ValueError(f'out[{k!r}] must be a contiguous {PLANE_DTYPES[k]} tensor {shape} on {dev}')
-        res[k] = given
+        shape, dtype = ((n, H, W, channels), 'uint8') if k == 'rgb' else ((n, H, W), PLANE_DTYPES[k])
+        res[k] = _tensor(shape, dtype, None if out is None else out[k], dev, stream, f'out[{k!r}]')
     return res, W, H
 
 
-def aux_args(tensors):
-    """(out pointer or None, Aux) of a plane_tensors dict: what an _aux entry takes."""
-    ptr = lambda k: tensors[k].data_ptr() if k in tensors else None  # noqa: E731
-    return ptr('rgb'), Aux(ptr('depth'), ptr('label'), ptr('surface'))
-
-
-def _call(entry, *args):
+def _call(entry, aux, *args):
+    """The one ctypes call of the renderer.  `args` are the plain entry's, the stream last; with `aux` (an Aux) the
+    call goes to the entry's _aux sibling, which takes a pointer to it in front of the stream."""
+    if aux is not None:
+        entry, args = entry + '_aux', (*args[:-1], C.byref(aux), args[-1])
     rc = getattr(load(), entry)(*args)
     if rc:
         check(rc, entry)
 
 
-def render_into(agent, grid, occ, n, atlas, out, width, height, channels, stream):
-    """One igw_render_pov call on raw pointers (ints); `atlas` is a device tensor [S, S, 4]."""
-    _call('igw_render_pov', agent, grid, occ, int(n), atlas.data_ptr(), int(atlas.shape[0]), out, int(width),
+def render_into(agent, grid, occ, n, atlas, out, width, height, channels, stream, aux=None):
+    """One igw_render_pov call on raw pointers (ints); `atlas` is a device tensor [S, S, 4].  With `aux`, an Aux, one
+    igw_render_pov_aux call (out may then be None); so for the two below."""
+    _call('igw_render_pov', aux, agent, grid, occ, int(n), atlas.data_ptr(), int(atlas.shape[0]), out, int(width),
           int(height), int(channels), stream)
 
 
 def render_episodes_into(records, n_records, first, length, frame0, start_grid, init_pose, m, max_length, atlas, out,
-                         n_frames, width, height, channels, stream):
+                         n_frames, width, height, channels, stream, aux=None):
     """One igw_render_episodes call on raw pointers (ints); `atlas` is a device tensor [S, S, 4]."""
-    _call('igw_render_episodes', records, int(n_records), first, length, frame0, start_grid, init_pose, int(m),
+    _call('igw_render_episodes', aux, records, int(n_records), first, length, frame0, start_grid, init_pose, int(m),
           int(max_length), atlas.data_ptr(), int(atlas.shape[0]), out, int(n_frames), int(width), int(height),
           int(channels), stream)
 
 
-def render_views_into(grids, grid_stride, n_grids, view_grid, pose, m, atlas, out, width, height, channels, stream):
+def render_views_into(grids, grid_stride, n_grids, view_grid, pose, m, atlas, out, width, height, channels, stream,
+                      aux=None):
     """One igw_render_views call on raw pointers (ints; view_grid may be None); `atlas` is a device tensor [S, S, 4]."""
-    _call('igw_render_views', grids, int(grid_stride), int(n_grids), view_grid, pose, int(m), atlas.data_ptr(),
+    _call('igw_render_views', aux, grids, int(grid_stride), int(n_grids), view_grid, pose, int(m), atlas.data_ptr(),
           int(atlas.shape[0]), out, int(width), int(height), int(channels), stream)
 
 
-def render_pov_aux_into(agent, grid, occ, n, atlas, out, width, height, channels, aux, stream):
-    """One igw_render_pov_aux call: render_into's arguments (out may be None) plus `aux`, an Aux."""
-    _call('igw_render_pov_aux', agent, grid, occ, int(n), atlas.data_ptr(), int(atlas.shape[0]), out, int(width),
-          int(height), int(channels), C.byref(aux), stream)
+_INTO = {'pov': render_into, 'episodes': render_episodes_into, 'views': render_views_into}
 
 
-def render_episodes_aux_into(records, n_records, first, length, frame0, start_grid, init_pose, m, max_length, atlas,
-                             out, n_frames, width, height, channels, aux, stream):
-    """One igw_render_episodes_aux call: render_episodes_into's arguments (out may be None) plus `aux`, an Aux."""
-    _call('igw_render_episodes_aux', records, int(n_records), first, length, frame0, start_grid, init_pose, int(m),
-          int(max_length), atlas.data_ptr(), int(atlas.shape[0]), out, int(n_frames), int(width), int(height),
-          int(channels), C.byref(aux), stream)
+def launch(kind, args, n, size, channels, outputs, out, atlas, dev, stream, alloc_stream=None):
+    """One render launch of n frames and what it wrote: the frame tensor, or with `outputs` the dict of targets().
+    `kind` is 'pov', 'episodes' or 'views' and `args` that wrapper's arguments in front of `atlas`; `stream` is the raw
+    stream of the launch, `alloc_stream` the torch stream to allocate on when it is not the current one.
 
-
-def render_views_aux_into(grids, grid_stride, n_grids, view_grid, pose, m, atlas, out, width, height, channels, aux,
-                          stream):
-    """One igw_render_views_aux call: render_views_into's arguments (out may be None) plus `aux`, an Aux."""
-    _call('igw_render_views_aux', grids, int(grid_stride), int(n_grids), view_grid, pose, int(m), atlas.data_ptr(),
-          int(atlas.shape[0]), out, int(width), int(height), int(channels), C.byref(aux), stream)
+    The entry rule, here and nowhere else: outputs=None calls the plain entry; a tuple calls the _aux entry with the
+    planes not asked for (and `out`, without 'rgb') NULL -- also for ('rgb',), which is the same frame from the other
+    kernel.  It touches the device only through data_ptr() and the ctypes call."""
+    res, W, H = targets(n, size, channels, outputs, out, dev, alloc_stream)
+    if outputs is None:
+        rgb, aux = res.data_ptr(), None
+    else:
+        ptr = lambda k: res[k].data_ptr() if k in res else None  # noqa: E731
+        rgb, aux = ptr('rgb'), Aux(ptr('depth'), ptr('label'), ptr('surface'))
+    frame = (rgb, n, W, H, channels) if kind == 'episodes' else (rgb, W, H, channels)
+    _INTO[kind](*args, atlas, *frame, stream, aux=aux)
+    return res
 
 
 # ---- reading the planes ---------------------------------------------------------------------------------------------

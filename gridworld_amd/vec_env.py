@@ -11,6 +11,8 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import codec as K
+from . import render as R
 
 
 def _as_rows(x, device, n=None):
@@ -55,8 +57,7 @@ class VecGridWorld:
         obs['pov'] alone."""
         if renderer not in (None, 'hip'):
             raise ValueError(f"unknown renderer {renderer!r}; the one renderer is 'hip'")
-        from . import render as _R
-        pov_outputs = _R.check_outputs(pov_outputs)
+        pov_outputs = R.check_outputs(pov_outputs)
         if renderer is None and pov_outputs != ('rgb',):
             raise ValueError("pov_outputs needs renderer='hip'")
         if render and not fake and renderer is None:
@@ -124,16 +125,11 @@ class VecGridWorld:
         self.config_epoch = 0
         self.render_size = (int(render_size[0]), int(render_size[1]))
         self._render_atlas = None
-        self.pov = None   # obs['pov'] of renderer='hip': [N, H, W, 3], rewritten by every reset / step
-        # what reset / step draw (renderer='hip'): output name -> persistent tensor; None for the default ('rgb',),
-        # which goes through the plain entry into self.pov
+        # what reset / step draw (renderer='hip'): the persistent tensors of pov_outputs; pov is obs['pov'], [N, H, W, 3]
         self.pov_outputs = pov_outputs if renderer == 'hip' else ()
-        self._pov_planes = None
-        if renderer == 'hip' and pov_outputs == ('rgb',):
-            self.pov = torch.empty((N, self.render_size[1], self.render_size[0], 3), dtype=torch.uint8, device=dev)
-        elif renderer == 'hip':
-            self._pov_planes, _, _ = _R.plane_tensors(N, self.render_size, pov_outputs, None, dev)
-            self.pov = self._pov_planes.get('rgb')
+        self._pov = _Pov(R.targets(N, self.render_size, 3, pov_outputs, None, dev)[0]) if renderer == 'hip' else None
+        self._rows = (self.agent_buf, self.grid_buf, self.occ_buf)   # the state a frame is drawn from
+        self.pov = self._pov.tensors.get('rgb') if self._pov else None
 
     def __del__(self):
         ctx = getattr(self, 'ctx', None)
@@ -162,8 +158,7 @@ class VecGridWorld:
         self.env_task = a[:, 2]                       # row of the task table
         self.episode = a[:, 3]                        # episodes started (keys the device-side task generators)
         self.grid = torch.as_strided(self.grid_buf, (N, 9, 11, 11), (L.GRID_STRIDE, 121, 11, 1))
-        self._obs = {'agentPos': self.agent_pos, 'inventory': self.inventory, 'compass': self.compass.unsqueeze(1),
-                     'grid': self.grid}
+        self._obs = _state_obs(self)
         self._dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
 
     def _stream(self):
@@ -325,9 +320,11 @@ class VecGridWorld:
         L.check(self.lib.igw_reset(self.ctx, None if m is None else C.c_void_p(m.data_ptr()),
                                    L.RESET_KEEP_SIZE if keep_size else 0, self._stream()), 'igw_reset')
         self._mask_keep = m
-        if self.pov_outputs:
-            return self._with_pov(self.obs())
-        return self.obs()
+        obs = self.obs()
+        if self._pov is not None:
+            self._draw()
+            self._pov.add_to(obs)
+        return obs
 
     @staticmethod
     def _check_camera(cam):
@@ -365,9 +362,16 @@ class VecGridWorld:
             if rc:
                 L.check(rc, 'igw_step_walking')
             self._act_keep = a
-            if self.pov_outputs:
-                return self._with_pov(self._obs.copy()), self.reward, self.done, {}
-            return self._obs.copy(), self.reward, self.done, {}
+        else:
+            self._step_dict(actions, N)
+        obs = self._obs.copy()
+        if self._pov is not None:
+            self._draw()
+            self._pov.add_to(obs)
+        return obs, self.reward, self.done, {}
+
+    def _step_dict(self, actions, N):
+        """The launch of step() for the two action spaces that take a dict: walking with discretize=False, flying."""
         dev = self.device
         self._check_camera(actions['camera'])
 
@@ -400,37 +404,16 @@ class VecGridWorld:
             if rc:
                 L.check(rc, 'igw_step_flying')
             self._act_keep = (mv, cam, inv, pl)
-        if self.pov_outputs:
-            return self._with_pov(self._obs.copy()), self.reward, self.done, {}
-        return self._obs.copy(), self.reward, self.done, {}
 
     # ---- first-person frames (libigw_render.so, include/igw_render.h) ----
-    def _with_pov(self, obs):
-        self._draw()
-        return self._pov_keys(obs)
-
     def _draw(self, stream=None):
-        """What reset / step draw after their launch (renderer='hip'): the persistent frame, or the persistent
-        outputs of pov_outputs in one igw_render_pov_aux launch; on the current stream unless one is given."""
-        stream = self._stream() if stream is None else stream
-        if self._pov_planes is None:
-            _render_rows(self, self.agent_buf, self.grid_buf, self.occ_buf, self.num_envs, self.pov, 3, None, stream)
-        else:
-            _render_rows(self, self.agent_buf, self.grid_buf, self.occ_buf, self.num_envs, self._pov_planes, 3, None,
-                         stream, outputs=self.pov_outputs)
-
-    def _pov_keys(self, obs):
-        if self._pov_planes is None:
-            obs['pov'] = self.pov
-        else:
-            _pov_obs(obs, self._pov_planes)
-        return obs
+        """What reset / step draw after their launch (renderer='hip'); on the current stream unless one is given."""
+        self._pov.draw(self, stream)
 
     def set_render_atlas(self, atlas):
         """The texture atlas of render_pov: uint8 [S, S, 4] (numpy or tensor, row 0 = the top image row), S a multiple
         of 8 up to 256 -- e.g. render.load_atlas('texture.png') of the reference for its look.  Default: the flat-colour
         atlas of render.default_atlas()."""
-        from . import render as R
         self._render_atlas = R.device_atlas(atlas, self.device)
 
     def _atlas(self):
@@ -448,13 +431,10 @@ class VecGridWorld:
         (include/igw_render.h); `out` is then a dict of preallocated tensors under those names, or None.
         codec='jpeg' returns (buf, sizes) of codec.encode_jpeg instead: the frames are drawn, then encoded at `quality`
         by a second launch on the same stream; `out` is then the (buf, sizes) pair to encode into, or None."""
-        from . import codec as K
-        if K.check_codec(codec, outputs):
-            frames = _render_rows(self, self.agent_buf, self.grid_buf, self.occ_buf, self.num_envs, None, channels,
-                                  size, self._stream())
-            return K.encode_jpeg(frames, quality, out=out, check_sizes=out is None)
-        return _render_rows(self, self.agent_buf, self.grid_buf, self.occ_buf, self.num_envs, out, channels, size,
-                            self._stream(), outputs=outputs)
+        def draw(out=None, outputs=None):
+            return _render_rows(self, out, channels, size, outputs, self._stream())
+        res = K.encoded(codec, outputs, quality, out, draw)
+        return draw(out, outputs) if res is None else res
 
     def render_views(self, poses, rows=None, what='grid', **kw):
         """Views of the batch from cameras of the caller's choice (visualizer.render_views): uint8 [M, H, W, channels]
@@ -677,7 +657,7 @@ class StepGraph:
         # step against 10.9 for the single chain -- while kernels of different STREAMS do run concurrently.)
         self.subs = env.split(chains) if chains > 1 else None   # (kept alive with the graphs)
         self.graphs = [self.graph] + [torch.cuda.CUDAGraph() for _ in range(chains - 1)]
-        if env.pov_outputs:
+        if env._pov is not None:
             env._atlas()   # (allocated before the capture)
         self.streams = [cap] + [torch.cuda.Stream(device=dev) for _ in range(chains - 1)]
         for k in range(chains):
@@ -692,7 +672,7 @@ class StepGraph:
                     L.check(fn(ctx, *(p + o for p, o in zip(ptrs[t], offs)), h), 'step (capture)')
                     if record:
                         self.outs[t, lo:lo + n].copy_(env.out_buf[lo:lo + n])
-                if env.pov_outputs:   # the frame (and planes) of the state after the last step
+                if env._pov is not None:   # the frame (and planes) of the state after the last step
                     (env if chains == 1 else self.subs[k])._draw(h)
             torch.cuda.current_stream(dev).wait_stream(st)
         if record:
@@ -726,7 +706,7 @@ class StepGraph:
             for st in self.streams:
                 cur.wait_stream(st)
         obs = env._obs.copy()
-        return (env._pov_keys(obs) if env.pov_outputs else obs), env.reward, env.done, {}
+        return (obs if env._pov is None else env._pov.add_to(obs)), env.reward, env.done, {}
 
 
 class SubBatch:
@@ -756,9 +736,10 @@ class SubBatch:
         self.compass, self.reward, self.done = parent.compass[sl], parent.reward[sl], parent.done[sl]
         self.grid = parent.grid[sl]
         self.render_size = parent.render_size
-        self.pov = None if parent.pov is None else parent.pov[sl]
         self.pov_outputs = parent.pov_outputs
-        self._pov_planes = None if parent._pov_planes is None else {k: t[sl] for k, t in parent._pov_planes.items()}
+        self._pov = None if parent._pov is None else parent._pov.rows(sl)
+        self._rows = tuple(t[sl] for t in parent._rows)
+        self.pov = self._pov.tensors.get('rgb') if self._pov else None
         self._inherit_sampling()
 
     def _inherit_sampling(self):
@@ -777,51 +758,37 @@ class SubBatch:
             self.ctx = None
 
     def obs(self):
-        o = {'agentPos': self.agent_pos, 'inventory': self.inventory, 'compass': self.compass.unsqueeze(1),
-             'grid': self.grid}
-        if self._pov_planes is not None:
-            _pov_obs(o, self._pov_planes)
-        elif self.pov is not None:
-            o['pov'] = self.pov
-        return o
+        o = _state_obs(self)
+        return o if self._pov is None else self._pov.add_to(o)
+
+    def _stream(self):
+        return C.c_void_p(self.stream.cuda_stream)
 
     def _draw(self, stream=None):
         """What reset / step draw after their launch (renderer='hip'), on this sub-batch's stream unless one is given
         (a capture's)."""
-        if not self.pov_outputs:
-            return
-        sl = slice(self.lo, self.lo + self.num_envs)
-        p = self.parent
-        if stream is None:
-            stream = C.c_void_p(self.stream.cuda_stream)
-            for t in (self._pov_planes.values() if self._pov_planes is not None else (self.pov,)):
-                t.record_stream(self.stream)
-        out = self.pov if self._pov_planes is None else self._pov_planes
-        _render_rows(self, p.agent_buf[sl], p.grid_buf[sl], p.occ_buf[sl], self.num_envs, out, 3, None, stream,
-                     outputs=None if self._pov_planes is None else self.pov_outputs)
+        if self._pov is not None:
+            self._pov.draw(self, stream, self.stream)
 
     def _atlas(self):
         return self.parent._atlas()
 
     def render_pov(self, out=None, channels=3, size=None, outputs=None, codec=None, quality=90):
         """VecGridWorld.render_pov for this sub-batch's rows, on its own stream."""
-        sl = slice(self.lo, self.lo + self.num_envs)
-        p = self.parent
-        from . import codec as K
-        if K.check_codec(codec, outputs):
-            frames = self.render_pov(None, channels, size)
-            for t in (out or ()):
-                t.record_stream(self.stream)
-            with torch.cuda.stream(self.stream):
-                res = K.encode_jpeg(frames, quality, out=out, check_sizes=out is None)
-            for t in res:
-                t.record_stream(self.stream)
-            return res
-        for t in (out.values() if isinstance(out, dict) else () if out is None else (out,)):
+        given = out.values() if isinstance(out, dict) else out if isinstance(out, (tuple, list)) else (out,)
+        for t in given:
             if torch.is_tensor(t):
                 t.record_stream(self.stream)
-        return _render_rows(self, p.agent_buf[sl], p.grid_buf[sl], p.occ_buf[sl], self.num_envs, out, channels, size,
-                            C.c_void_p(self.stream.cuda_stream), stream_obj=self.stream, outputs=outputs)
+
+        def draw(out=None, outputs=None):
+            return _render_rows(self, out, channels, size, outputs, self._stream(), self.stream)
+        with torch.cuda.stream(self.stream):
+            res = K.encoded(codec, outputs, quality, out, draw)
+        if res is None:
+            return draw(out, outputs)
+        for t in res:
+            t.record_stream(self.stream)
+        return res
 
     def step_walking_ptr(self, actions_i32):
         """actions_i32: contiguous int32 device tensor [n]; launched on this sub-batch's stream (the tensor is
@@ -829,12 +796,11 @@ class SubBatch:
         if actions_i32.numel() != self.num_envs:
             raise ValueError(f'walking action needs {self.num_envs} entries, got {actions_i32.numel()}')
         actions_i32.record_stream(self.stream)
-        L.check(self.lib.igw_step_walking(self.ctx, actions_i32.data_ptr(), C.c_void_p(self.stream.cuda_stream)),
-                'igw_step_walking')
+        L.check(self.lib.igw_step_walking(self.ctx, actions_i32.data_ptr(), self._stream()), 'igw_step_walking')
         self._draw()
 
     def reset(self):
-        L.check(self.lib.igw_reset(self.ctx, None, 0, C.c_void_p(self.stream.cuda_stream)), 'igw_reset')
+        L.check(self.lib.igw_reset(self.ctx, None, 0, self._stream()), 'igw_reset')
         self._draw()
         return self.obs()
 
@@ -846,27 +812,49 @@ class SubBatch:
         torch.cuda.current_stream(self.device).wait_stream(self.stream)
 
 
-def _pov_obs(obs, planes):
-    """Adds the persistent outputs of pov_outputs to an obs dict: 'rgb' as 'pov', the planes under their names."""
-    for k, t in planes.items():
-        obs['pov' if k == 'rgb' else k] = t
+def _state_obs(e):
+    """The four state keys of an observation: views of the records of a VecGridWorld or of a SubBatch's rows."""
+    return {'agentPos': e.agent_pos, 'inventory': e.inventory, 'compass': e.compass.unsqueeze(1), 'grid': e.grid}
 
 
-def _render_rows(env, agent, grid, occ, n, out, channels, size, stream, stream_obj=None, outputs=None):
-    """igw_render_pov (outputs=None) or igw_render_pov_aux over rows of a batch's state buffers (a whole VecGridWorld
-    or a SubBatch's slice)."""
-    from . import render as R
-    if outputs is not None:
-        res, W, H = R.plane_tensors(n, size if size is not None else env.render_size, outputs, out, env.device,
-                                    stream_obj, channels=channels)
-        rgb, aux = R.aux_args(res)
-        R.render_pov_aux_into(agent.data_ptr(), grid.data_ptr(), occ.data_ptr(), n, env._atlas(), rgb, W, H, channels,
-                              aux, stream)
-        return res
-    out, W, H = R.frame_tensor(n, size if size is not None else env.render_size, channels, out, env.device, stream_obj)
-    R.render_into(agent.data_ptr(), grid.data_ptr(), occ.data_ptr(), n, env._atlas(), out.data_ptr(), W, H, channels,
-                  stream)
-    return out
+class _Pov:
+    """The persistent outputs of renderer='hip': output name -> tensor as pov_outputs names them, for the whole batch
+    or, through rows(), for a SubBatch's slice of the same memory.  The default, ('rgb',), is drawn by the plain entry
+    (render.launch with outputs=None); anything else by one _aux launch."""
+
+    def __init__(self, tensors):
+        self.tensors = tensors
+        self.plain = tuple(tensors) == ('rgb',)
+
+    def rows(self, sl):
+        return _Pov({k: t[sl] for k, t in self.tensors.items()})
+
+    def draw(self, env, stream=None, own=None):
+        """Draws the tensors from env's state rows on `stream`; without one on the env's own, where the tensors are
+        then marked as in use if that is a side stream, `own` (a SubBatch's)."""
+        if stream is None:
+            stream = env._stream()
+            for t in self.tensors.values() if own is not None else ():
+                t.record_stream(own)
+        if self.plain:
+            _render_rows(env, self.tensors['rgb'], 3, None, None, stream)
+        else:
+            _render_rows(env, self.tensors, 3, None, tuple(self.tensors), stream)
+
+    def add_to(self, obs):
+        """Adds the tensors to an observation dict, 'rgb' as 'pov' and the planes under their names; returns it."""
+        for k, t in self.tensors.items():
+            obs['pov' if k == 'rgb' else k] = t
+        return obs
+
+
+def _render_rows(env, out, channels, size, outputs, stream, alloc_stream=None):
+    """One igw_render_pov launch (render.launch) over the state rows of a whole VecGridWorld or of a SubBatch."""
+    agent, grid, occ = env._rows
+    n = env.num_envs
+    return R.launch('pov', (agent.data_ptr(), grid.data_ptr(), occ.data_ptr(), n), n,
+                    size if size is not None else env.render_size, channels, outputs, out, env._atlas(), env.device,
+                    stream, alloc_stream)
 
 
 def task_eval(targets, grids, full_grids=None, invariant=None, device='cuda:0'):

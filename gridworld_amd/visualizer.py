@@ -15,6 +15,7 @@ import math
 
 import numpy as np
 
+from . import codec as K
 from . import render as R
 
 GRID_SHAPE = (9, 11, 11)
@@ -105,12 +106,11 @@ def render_views(grids, poses, view_grid=None, size=(64, 64), channels=3, atlas=
                  `quality` by a second launch on the same stream; `out` is then the (buf, sizes) pair to encode into.
     """
     import torch
-    from . import codec as K
-    if K.check_codec(codec, outputs):
-        frames = render_views(grids, poses, view_grid, size, channels, atlas, None, device)
-        return K.encode_jpeg(frames, quality, out=out, check_sizes=out is None)
-    if outputs is not None:
-        outputs = R.check_outputs(outputs)
+    res = K.encoded(codec, outputs, quality, out,
+                    lambda: render_views(grids, poses, view_grid, size, channels, atlas, None, device))
+    if res is not None:
+        return res
+    outputs = R.check_outputs(outputs)
     R.need_device('render_views')
     dev = torch.device(device)
     if dev.type == 'cuda' and dev.index is None:
@@ -140,18 +140,9 @@ def render_views(grids, poses, view_grid=None, size=(64, 64), channels=3, atlas=
             raise ValueError(f'view_grid must index the {n_grids} grids, got {int(idx.min())}..{int(idx.max())}')
         vg = torch.from_numpy(idx.astype(np.int32)).to(dev)
     a = R.device_atlas(atlas, dev)
-    if outputs is not None:
-        res, W, H = R.plane_tensors(m, size, outputs, out, dev, channels=channels)
-        rgb, aux = R.aux_args(res)
-        with torch.cuda.device(dev):
-            R.render_views_aux_into(g.data_ptr(), stride, n_grids, None if vg is None else vg.data_ptr(), p.data_ptr(),
-                                    m, a, rgb, W, H, channels, aux, torch.cuda.current_stream(dev).cuda_stream)
-        return res
-    out, W, H = R.frame_tensor(m, size, channels, out, dev)
     with torch.cuda.device(dev):
-        R.render_views_into(g.data_ptr(), stride, n_grids, None if vg is None else vg.data_ptr(), p.data_ptr(), m, a,
-                            out.data_ptr(), W, H, channels, torch.cuda.current_stream(dev).cuda_stream)
-    return out
+        return R.launch('views', (g.data_ptr(), stride, n_grids, None if vg is None else vg.data_ptr(), p.data_ptr(), m),
+                        m, size, channels, outputs, out, a, dev, torch.cuda.current_stream(dev).cuda_stream)
 
 
 # ---- the reference's Visualizer -----------------------------------------------------------------------------------
@@ -268,37 +259,30 @@ class Visualizer:
         reference (a list of blocks counted from the ground level 0 rather than the world's -1).  outputs (a tuple
         of 'rgb', 'depth', 'label', 'surface'; render_views) gives a dict name -> numpy array instead: the frame
         and / or the [H, W] planes, e.g. surface for picking the cell under a pixel (render.decode_surface)."""
-        if outputs is not None:
-            outputs = R.check_outputs(outputs)
+        outputs = R.check_outputs(outputs)
         self.set_agent_state(position, rotation)
         if blocks is not None:
             self.replace_world(blocks)
         out = render_views(self.grid()[None], self.pose()[None], size=self.render_size, atlas=self._atlas(),
                            device=self.device, outputs=outputs)
-        if outputs is not None:
-            return {k: v[0].cpu().numpy() for k, v in out.items()}
-        return out[0].cpu().numpy()
+        return _to_host(out, 0)
 
     def render_batch(self, positions, rotations, blocks=None, outputs=None):
         """T frames in one launch: numpy uint8 [T, H, W, 3].  positions [T, 3], rotations [T, 2].  blocks=None: the
         current world from the T poses (one grid, T views).  Otherwise `blocks` is a list of T block lists, frame t
         showing blocks[t] the way render(blocks=) places them (y - 1); the world is left holding the last one, and
         the camera the last pose, as after T render() calls.  outputs: as for render(), a dict of [T, ...] arrays."""
-        if outputs is not None:
-            outputs = R.check_outputs(outputs)
+        outputs = R.check_outputs(outputs)
         poses, grids = self.batch_inputs(positions, rotations, blocks)
         view_grid = np.zeros(len(poses), np.int32) if blocks is None else None
         out = render_views(grids, poses, view_grid=view_grid, size=self.render_size, atlas=self._atlas(),
                            device=self.device, outputs=outputs)
-        if outputs is not None:
-            return {k: v.cpu().numpy() for k, v in out.items()}
-        return out.cpu().numpy()
+        return _to_host(out)
 
     def render_video(self, output, positions, rotations, blocks=None, fps=60, quality=90):
         """The frames of render_batch(positions, rotations, blocks) as a video: ONE render launch, ONE encode launch
         (codec.encode_jpeg at `quality`), then {output}.avi, Motion-JPEG at `fps` (codec.write_avi).  Returns the
         path.  The camera and the world are left as after render_batch."""
-        from . import codec as K
         poses, grids = self.batch_inputs(positions, rotations, blocks)
         view_grid = np.zeros(len(poses), np.int32) if blocks is None else None
         buf, sizes = render_views(grids, poses, view_grid=view_grid, size=self.render_size, atlas=self._atlas(),
@@ -324,6 +308,13 @@ class Visualizer:
         if len(poses):
             self.set_agent_state(poses[-1, :3], poses[-1, 3:])
         return poses, grids
+
+
+def _to_host(res, index=slice(None)):
+    """What render_views returned, a tensor or a dict of them, as numpy: all of it, or frame `index`."""
+    if isinstance(res, dict):
+        return {k: v[index].cpu().numpy() for k, v in res.items()}
+    return res[index].cpu().numpy()
 
 
 def _vector(v, n, name):

@@ -1,4 +1,13 @@
 """Wrappers of the reference that sit on the step path (gridworld/wrappers.py)."""
+import os
+import uuid
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from . import codec as K
+from . import render as R
 from . import spaces
 from .env import Wrapper  # noqa: F401  (gridworld/env.py:306-314; re-exported: the reference imports gym.Wrapper here)
 
@@ -53,9 +62,6 @@ class EpisodeLogger:
 
     def __init__(self, vec, n_envs=1, path='episodes', desc='', glob_step=0, capacity=None, pov=False,
                  pov_outputs=('rgb',), pov_codec=None, pov_quality=90):
-        import numpy as np
-        from . import codec as K, render as R
-        self.np = np
         self.vec, self.path, self.desc, self.glob_step = vec, path, desc, glob_step
         self.pov = bool(pov)
         self.pov_outputs = R.check_outputs(pov_outputs)
@@ -76,8 +82,7 @@ class EpisodeLogger:
         self.desc, self.glob_step = desc, glob_step
 
     def _decode(self, env, slot, task, length):
-        np, v = self.np, self.vec
-        from . import _lib as L
+        v = self.vec
         raw = self.records[env, slot, :length].cpu().numpy()   # record layout: include/igw.h (igw_set_trajectory_log)
         f32 = raw[:, :28].copy().view(np.float32).reshape(length, 7)
         inv = raw[:, 28:40].copy().view(np.int16).reshape(length, 6)
@@ -111,9 +116,6 @@ class EpisodeLogger:
     def _render(self, todo):
         """pov frames (and planes) of the episodes (env, slot, task, length, episode) in one igw_render_episodes (or
         _aux) launch on the env's stream: a list of dicts array name -> [length + 1, H, W, ...] array."""
-        np = self.np
-        import torch
-        from . import render as R
         v = self.vec
         if not todo:
             return []
@@ -126,22 +128,16 @@ class EpisodeLogger:
         frame0_d = torch.from_numpy(frame0[:-1].copy()).to(dev)
         start = v.task_start.index_select(0, rows)                                     # [m, 1104] i8
         pose = v.task_meta.index_select(0, rows)[:, :40].contiguous().view(torch.float64)   # [m, 5] x, y, z, yaw, pitch
-        W, H = v.render_size
-        n_frames = int(frame0[-1])
         args = (self.records.data_ptr(), self.records.shape[0] * 2 * cap, first.data_ptr(), length_d.data_ptr(),
-                frame0_d.data_ptr(), start.data_ptr(), pose.data_ptr(), len(todo), cap, v._atlas())
-        if self.pov_outputs == ('rgb',):
-            out = torch.empty((n_frames, H, W, 3), dtype=torch.uint8, device=dev)
-            R.render_episodes_into(*args, out.data_ptr(), n_frames, W, H, 3, v._stream())
-            res = {'rgb': out}
-        else:
-            res, _, _ = R.plane_tensors(n_frames, (W, H), self.pov_outputs, None, dev)
-            rgb, aux = R.aux_args(res)
-            R.render_episodes_aux_into(*args, rgb, n_frames, W, H, 3, aux, v._stream())
+                frame0_d.data_ptr(), start.data_ptr(), pose.data_ptr(), len(todo), cap)
+        # as for VecGridWorld, the default ('rgb',) is the plain entry
+        outputs = None if self.pov_outputs == ('rgb',) else self.pov_outputs
+        res = R.launch('episodes', args, int(frame0[-1]), v.render_size, 3, outputs, None, v._atlas(), dev, v._stream())
+        if outputs is None:
+            res = {'rgb': res}
         jpegs = None
-        if self.pov_codec:
-            from . import codec as K
-            jpegs = K.jpeg_bytes(*K.encode_jpeg(res.pop('rgb'), self.pov_quality))   # on v._stream(), the current one
+        if self.pov_codec:   # (on v._stream(), the current one)
+            jpegs = K.jpeg_bytes(*K.encoded(self.pov_codec, None, self.pov_quality, None, lambda: res.pop('rgb')))
         host = {'pov' if k == 'rgb' else k: t.cpu().numpy() for k, t in res.items()}
         eps = [{k: h[frame0[i]:frame0[i + 1]] for k, h in host.items()} for i in range(len(todo))]
         if jpegs is not None:
@@ -153,22 +149,16 @@ class EpisodeLogger:
         """Writes an episode's frames (a dict collect() returned) as a Motion-JPEG AVI at `path`: its `pov_jpeg` streams
         as they are, or its raw `pov` frames encoded first (one igw_jpeg_encode launch at pov_quality).  Returns the
         path."""
-        from . import codec as K
         jpegs = episode.get('pov_jpeg')
         if jpegs is None:
             if 'pov' not in episode:
                 raise ValueError('the episode has no frames: log with EpisodeLogger(pov=True)')
-            import torch
-            jpegs = K.jpeg_bytes(*K.encode_jpeg(torch.from_numpy(self.np.ascontiguousarray(episode['pov']))
+            jpegs = K.jpeg_bytes(*K.encode_jpeg(torch.from_numpy(np.ascontiguousarray(episode['pov']))
                                                 .to(self.vec.device), self.pov_quality))
         return K.write_avi(path, jpegs, self.vec.render_size, fps)
 
     def collect(self, dump=True):
         """Decodes (and with dump=True writes) every logged episode that finished since the last call."""
-        import os
-        import uuid
-        np = self.np
-        import torch
         torch.cuda.synchronize(self.vec.device)
         heads = self.heads.cpu().numpy()
         todo = []

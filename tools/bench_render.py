@@ -341,9 +341,9 @@ def bench_ab(iters, warmup, repeats, episodes, steps, other):
         us = {'this': [], 'parent': []}
         for _ in range(repeats):
             for who, lib in (('this', mine), ('parent', other)):
-                R._lib = lib
+                R.BINDING.lib = lib
                 us[who].append(_time(fn, its, warmup))
-        R._lib = mine
+        R.BINDING.lib = mine
         res[name] = {who: _spread(v) for who, v in us.items()}
         res[name]['this_median_within_parent_spread_or_faster'] = \
             res[name]['this']['us_per_launch_median'] <= res[name]['parent']['us_per_launch_max']
@@ -359,7 +359,7 @@ def _use_library(path):
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.restype, fn.argtypes = res, args
-    R._lib = lib
+    R.BINDING.lib = lib
 
 
 def _git_commit():
@@ -395,7 +395,7 @@ def main():
             sys.exit('--mode ab needs --lib, the other build')
         mine = R.load()
         _use_library(a.lib)
-        other, R._lib = R._lib, mine
+        other, R.BINDING.lib = R.BINDING.lib, mine
         line = {'tool': 'tools/bench_render.py', 'render_build_id': R.build_id(),
                 'parent_render_build_id': other.igw_render_build_id().decode(),
                 'device': torch.cuda.get_device_name(0),
