@@ -12,6 +12,6 @@ from .tasks import Task, Tasks, CustomTasks, RandomTasks, Subtasks, dummy_task  
 from . import workloads  # noqa: F401,E402
 from . import visualizer  # noqa: F401,E402
 from .visualizer import Visualizer, look_at, orbit_poses, render_views  # noqa: F401,E402
-from .render import decode_surface, unproject  # noqa: F401,E402
+from .render import ObsSpec, decode_surface, unproject  # noqa: F401,E402
 from . import codec  # noqa: F401,E402
 from .codec import encode_jpeg, jpeg_bytes  # noqa: F401,E402

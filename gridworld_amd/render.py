@@ -14,6 +14,7 @@ import os
 import sys
 
 import numpy as np
+import torch
 
 from . import build as _build
 
@@ -22,6 +23,12 @@ CSRC = os.path.join(HERE, 'csrc', 'render')
 LIB = os.path.join(HERE, 'libigw_render.so')
 SOURCES = [os.path.join(CSRC, 'igw_render.hip')]
 HEADERS = [os.path.join(CSRC, 'igw_render_frame.h'), os.path.join(HERE, '..', 'include', 'igw_render.h')]
+# the training-layout observation is a library of its own (include/igw_render_obs.h): the same ray caster, compiled
+# again, so that libigw_render.so and its build id stay what they were
+OBS_LIB = os.path.join(HERE, 'libigw_render_obs.so')
+OBS_SOURCES = [os.path.join(CSRC, 'igw_render_obs.hip')]
+OBS_HEADERS = HEADERS + [os.path.join(CSRC, 'igw_render_obs_stage.h'),
+                         os.path.join(HERE, '..', 'include', 'igw_render_obs.h')]
 VERSION = 1
 MAX_SIDE = 1024
 MAX_ATLAS = 256
@@ -42,9 +49,19 @@ SIGNATURES = {
 SIGNATURES.update({name + '_aux': (res, args[:-1] + [_vp] + args[-1:])
                    for name, (res, args) in list(SIGNATURES.items()) if args})
 EXPORTS = list(SIGNATURES)
+# every symbol include/igw_render_obs.h declares; igw_render_pov_obs is the plain pov entry without `channels`, with
+# `const igw_render_obs* obs` in front of `stream`
+OBS_SIGNATURES = {
+    'igw_render_obs_build_id': (C.c_char_p, []),
+    'igw_render_obs_last_error': (C.c_char_p, []),
+    'igw_render_pov_obs': (C.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _vp]),
+}
+OBS_EXPORTS = list(OBS_SIGNATURES)
 # the library as build.py builds it: the step library's FLAGS, an id of its own (igw_render_build_id())
 LIBRARY = _build.Library(LIB, SOURCES, HEADERS, 'igw-render-build-id:', 'IGW_RENDER_BUILD_ID', deps=[__file__])
 source_hash, built_id, is_stale = LIBRARY.source_hash, LIBRARY.built_id, LIBRARY.is_stale
+OBS_LIBRARY = _build.Library(OBS_LIB, OBS_SOURCES, OBS_HEADERS, 'igw-render-obs-build-id:', 'IGW_RENDER_OBS_BUILD_ID',
+                             deps=[__file__])
 
 
 class RenderError(RuntimeError):
@@ -56,6 +73,56 @@ class Aux(C.Structure):
     _fields_ = [('depth', _vp), ('label', _vp), ('surface', _vp)]
 
 
+class Obs(C.Structure):
+    """igw_render_obs: the observation of igw_render_pov_obs (`data` and `restart` are device pointers)."""
+    _fields_ = [('data', _vp), ('dtype', _i32), ('gray', _i32), ('stack', _i32), ('fill', _i32),
+                ('scale', C.c_float), ('bias', C.c_float), ('restart', _vp), ('restart_stride', _i64)]
+
+
+OBS_DTYPES = {torch.uint8: 0, torch.float16: 1, torch.bfloat16: 2, torch.float32: 3}   # IGW_OBS_*
+MAX_STACK = 8
+
+
+class ObsSpec:
+    """The layout of a training observation (include/igw_render_obs.h: igw_render_obs): `dtype` torch.uint8, float16,
+    bfloat16 or float32; gray = one luminance plane in place of R, G, B; stack = K, the last K frames (1..8), oldest
+    first; the float types hold value * scale + bias (uint8 takes scale 1, bias 0).  Validated on construction
+    (ValueError; no device needed)."""
+
+    def __init__(self, dtype=torch.uint8, gray=False, stack=1, scale=1.0, bias=0.0):
+        if isinstance(dtype, str):
+            dtype = getattr(torch, dtype, dtype)
+        if dtype not in OBS_DTYPES:
+            raise ValueError(f'dtype must be torch.uint8, float16, bfloat16 or float32, got {dtype!r}')
+        if isinstance(stack, bool) or int(stack) != stack or not 1 <= int(stack) <= MAX_STACK:
+            raise ValueError(f'stack must be an integer in 1..{MAX_STACK}, got {stack!r}')
+        scale, bias = float(scale), float(bias)
+        top = float(np.finfo(np.float32).max)   # (the kernel takes them as float32)
+        if not (abs(scale) <= top and abs(bias) <= top):
+            raise ValueError(f'scale and bias must be finite float32 values, got {scale!r}, {bias!r}')
+        if dtype is torch.uint8 and (scale != 1.0 or bias != 0.0):
+            raise ValueError('a uint8 observation takes scale 1 and bias 0')
+        self.dtype, self.gray, self.stack, self.scale, self.bias = dtype, bool(gray), int(stack), scale, bias
+        self.planes = 1 if self.gray else 3
+
+    @classmethod
+    def of(cls, spec):
+        """An ObsSpec as it is, or one from a dict of its arguments."""
+        if isinstance(spec, cls):
+            return spec
+        if isinstance(spec, dict):
+            return cls(**spec)
+        raise ValueError(f'an observation is an ObsSpec or a dict of its arguments, got {type(spec).__name__}')
+
+    def shape(self, n, size):
+        """(n, K * planes, H, W) for size = (W, H): slot k holds channels [k * planes, (k + 1) * planes)."""
+        return (int(n), self.stack * self.planes, int(size[1]), int(size[0]))
+
+    def __repr__(self):
+        return (f'ObsSpec(dtype={self.dtype}, gray={self.gray}, stack={self.stack}, scale={self.scale}, '
+                f'bias={self.bias})')
+
+
 # the outputs of a render call with `outputs=`: 'rgb' is the colour frame, the others the planes (name -> dtype name)
 OUTPUTS = ('rgb', 'depth', 'label', 'surface')
 PLANE_DTYPES = {'depth': 'float32', 'label': 'uint8', 'surface': 'int16'}
@@ -64,12 +131,16 @@ GROUND_FACE, CELLS, GROUND_SPAN = 6, 1089, 37
 
 
 def build(force=False, verbose=False):
+    """Builds both renderer libraries; returns the path of libigw_render.so."""
+    OBS_LIBRARY.build(force, verbose=verbose)
     return LIBRARY.build(force, verbose=verbose)
 
 
 BINDING = _build.Binding(LIBRARY, SIGNATURES, RenderError, 'igw_render_last_error', 'igw_render_build_id',
                          'gridworld_amd.render', 'igw_render_pov')
 load, check, build_id = BINDING.load, BINDING.check, BINDING.build_id
+OBS_BINDING = _build.Binding(OBS_LIBRARY, OBS_SIGNATURES, RenderError, 'igw_render_obs_last_error',
+                             'igw_render_obs_build_id', 'gridworld_amd.render', 'igw_render_pov_obs')
 
 
 def need_device(what):
@@ -193,9 +264,10 @@ def _call(entry, aux, *args):
     call goes to the entry's _aux sibling, which takes a pointer to it in front of the stream."""
     if aux is not None:
         entry, args = entry + '_aux', (*args[:-1], C.byref(aux), args[-1])
-    rc = getattr(load(), entry)(*args)
+    binding = OBS_BINDING if entry in OBS_SIGNATURES else BINDING   # (the library that exports the entry)
+    rc = getattr(binding.load(), entry)(*args)
     if rc:
-        check(rc, entry)
+        binding.check(rc, entry)
 
 
 def render_into(agent, grid, occ, n, atlas, out, width, height, channels, stream, aux=None):
@@ -220,6 +292,12 @@ def render_views_into(grids, grid_stride, n_grids, view_grid, pose, m, atlas, ou
           int(atlas.shape[0]), out, int(width), int(height), int(channels), stream)
 
 
+def obs_into(agent, grid, occ, n, atlas, out, width, height, obs, stream):
+    """One igw_render_pov_obs call on raw pointers (ints); `obs` is an Obs, `out` the frame [n, H, W, 3] or None."""
+    _call('igw_render_pov_obs', None, agent, grid, occ, int(n), atlas.data_ptr(), int(atlas.shape[0]), out, int(width),
+          int(height), C.byref(obs), stream)
+
+
 _INTO = {'pov': render_into, 'episodes': render_episodes_into, 'views': render_views_into}
 
 
@@ -240,6 +318,32 @@ def launch(kind, args, n, size, channels, outputs, out, atlas, dev, stream, allo
     frame = (rgb, n, W, H, channels) if kind == 'episodes' else (rgb, W, H, channels)
     _INTO[kind](*args, atlas, *frame, stream, aux=aux)
     return res
+
+
+def launch_obs(args, n, size, spec, out, frame, restart, fill, atlas, dev, stream, alloc_stream=None):
+    """One igw_render_pov_obs launch of n envs and the observation it wrote, `spec`.shape(n, size) of spec.dtype: `out`
+    (the stack the previous launch left, shifted in place) or a new tensor, which is always filled.  `args` are
+    obs_into's arguments in front of `atlas`; `frame` is None (no frame: the entry gets out = NULL) or the uint8
+    [n, H, W, 3] tensor the frame goes to; `restart` is None or a 1-D uint8 / bool tensor of n elements on `dev`, at
+    any stride (env i restarts its stack where element i is not 0); `fill` restarts every env.  With `out` nothing is
+    allocated.  It touches the device only through data_ptr() and the ctypes call."""
+    W, H = int(size[0]), int(size[1])
+    if not (1 <= W <= MAX_SIDE and 1 <= H <= MAX_SIDE):
+        raise ValueError(f'size must be within 1..{MAX_SIDE} each way, got {size}')
+    name = str(spec.dtype).split('.')[-1]
+    data = _tensor(spec.shape(n, (W, H)), name, out, dev, alloc_stream, 'out')
+    if frame is not None:
+        frame = _tensor((n, H, W, 3), 'uint8', frame, dev, alloc_stream, 'frame')
+    ptr, stride = None, 0
+    if restart is not None:
+        if (not torch.is_tensor(restart) or restart.dtype not in (torch.uint8, torch.bool) or restart.dim() != 1
+                or restart.shape[0] != n or restart.device != dev or (n > 1 and restart.stride(0) < 1)):
+            raise ValueError(f'restart must be a uint8 or bool tensor [{n}] on {dev}')
+        ptr, stride = restart.data_ptr(), max(1, restart.stride(0))
+    obs = Obs(data.data_ptr(), OBS_DTYPES[spec.dtype], int(spec.gray), spec.stack, int(bool(fill) or out is None),
+              spec.scale, spec.bias, ptr, stride)
+    obs_into(*args, atlas, None if frame is None else frame.data_ptr(), W, H, obs, stream)
+    return data
 
 
 # ---- reading the planes ---------------------------------------------------------------------------------------------

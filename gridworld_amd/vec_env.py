@@ -39,7 +39,7 @@ class VecGridWorld:
                  size_reward=True, max_steps=250, right_placement_scale=1., wrong_placement_scale=0.1,
                  discretize=True, autoreset=False, num_tasks=None, lanes_per_env=0, debug_flags=0, env_index_base=0,
                  host_records=False, render=False, render_size=(64, 64), target_in_obs=False, vector_state=True, name='', fake=False,
-                 renderer=None, pov_outputs=('rgb',)):
+                 renderer=None, pov_outputs=('rgb',), pov_obs=None, pov_frame=True):
         """create_env's keyword arguments (gridworld/env.py:333-338) plus the batch's own: num_envs, device,
         autoreset (reset inside step), num_tasks (rows of the task table, default num_envs), lanes_per_env
         (0 = automatic), env_index_base (global index of env 0: rank / sub-batch offset), debug_flags (IGW_DIAG
@@ -54,12 +54,29 @@ class VecGridWorld:
         pov_outputs (with renderer='hip') names what that launch writes: 'rgb' is obs['pov']; 'depth' (float32),
         'label' (uint8) and 'surface' (int16) add obs keys of those names, persistent [N, H, W] planes rewritten by
         every reset() / step() in the same launch (include/igw_render.h: igw_render_aux).  The default, ('rgb',), is
-        obs['pov'] alone."""
+        obs['pov'] alone.
+        pov_obs (with renderer='hip'; a render.ObsSpec or a dict of its arguments) adds obs['pov_obs'], the observation
+        a policy network reads: a persistent [N, K * planes, H, W] tensor of the spec's dtype -- channel-first, grey or
+        RGB, scaled, the last K frames stacked -- written by the one launch that draws obs['pov']
+        (include/igw_render_obs.h: igw_render_pov_obs).  The env owns the stack's episode boundaries: reset() fills every env's stack with its
+        frame, reset(mask) the masked envs', step() with autoreset=True those of the envs whose episode just ended (the
+        frame drawn then already shows the next episode), step() with autoreset=False none (the terminal frame joins
+        its own episode's stack); after anything that moves the state without drawing (rollout, rollout_actions,
+        load_state_dict, set_tasks) the next draw fills.  pov_frame=False (only with pov_obs) drops obs['pov'] and its
+        store.  pov_obs goes with pov_outputs=('rgb',) only."""
         if renderer not in (None, 'hip'):
             raise ValueError(f"unknown renderer {renderer!r}; the one renderer is 'hip'")
         pov_outputs = R.check_outputs(pov_outputs)
         if renderer is None and pov_outputs != ('rgb',):
             raise ValueError("pov_outputs needs renderer='hip'")
+        if pov_obs is not None:
+            if renderer is None:
+                raise ValueError("pov_obs needs renderer='hip'")
+            if pov_outputs != ('rgb',):
+                raise ValueError("pov_obs goes with pov_outputs=('rgb',) only: the planes are not written in this layout")
+            pov_obs = R.ObsSpec.of(pov_obs)
+        elif not pov_frame:
+            raise ValueError('pov_frame=False needs pov_obs (there would be nothing to draw)')
         if render and not fake and renderer is None:
             raise NotImplementedError("render=True needs renderer='hip' (the batched HIP ray caster of the "
                                       "first-person frame); or pass render=False")
@@ -127,9 +144,20 @@ class VecGridWorld:
         self._render_atlas = None
         # what reset / step draw (renderer='hip'): the persistent tensors of pov_outputs; pov is obs['pov'], [N, H, W, 3]
         self.pov_outputs = pov_outputs if renderer == 'hip' else ()
-        self._pov = _Pov(R.targets(N, self.render_size, 3, pov_outputs, None, dev)[0]) if renderer == 'hip' else None
+        self._pov = None
+        if renderer == 'hip' and pov_obs is None:
+            self._pov = _Pov(R.targets(N, self.render_size, 3, pov_outputs, None, dev)[0])
+        elif renderer == 'hip':   # the stack, and the frame unless pov_frame=False: one igw_render_pov_obs launch
+            W, H = self.render_size
+            frame = {'rgb': R.targets(N, self.render_size, 3, None, None, dev)[0]} if pov_frame else {}
+            self._pov = _Pov(frame, pov_obs, torch.zeros(pov_obs.shape(N, (W, H)), dtype=pov_obs.dtype, device=dev))
+        self.pov_obs_spec = pov_obs
+        # the next draw restarts every env's stack: set by whatever moves the state without drawing.  _obs_flags are
+        # the same flag and a scratch mask as device bytes per env, for draws inside a captured graph (StepGraph).
+        self._obs_fill, self._obs_flags = True, None
         self._rows = (self.agent_buf, self.grid_buf, self.occ_buf)   # the state a frame is drawn from
         self.pov = self._pov.tensors.get('rgb') if self._pov else None
+        self.pov_obs = self._pov.obs if self._pov else None
 
     def __del__(self):
         ctx = getattr(self, 'ctx', None)
@@ -217,6 +245,7 @@ class VecGridWorld:
                 self.env_task.zero_()
         self._keep = (tgt, st, fg, inv, pose)  # keep inputs alive until the async kernel ran
         self._have_tasks = True
+        self._obs_moved()
 
     def set_task_sampling(self, enabled=True, seed=0, n_tasks=None):
         """Draw every env's task uniformly from the filled rows of the task table at each reset / auto-reset, on
@@ -296,6 +325,7 @@ class VecGridWorld:
         for k in self._STATE_KEYS:
             getattr(self, k).copy_(state[k])
         self._have_tasks = True
+        self._obs_moved()
 
     # ---- reset / step ----
     def _need_tasks(self):
@@ -322,7 +352,7 @@ class VecGridWorld:
         self._mask_keep = m
         obs = self.obs()
         if self._pov is not None:
-            self._draw()
+            self._draw(restart=None if m is None else m.reshape(-1), fill=m is None)
             self._pov.add_to(obs)
         return obs
 
@@ -366,7 +396,7 @@ class VecGridWorld:
             self._step_dict(actions, N)
         obs = self._obs.copy()
         if self._pov is not None:
-            self._draw()
+            self._draw(restart=self.done if self.autoreset else None)
             self._pov.add_to(obs)
         return obs, self.reward, self.done, {}
 
@@ -406,9 +436,40 @@ class VecGridWorld:
             self._act_keep = (mv, cam, inv, pl)
 
     # ---- first-person frames (libigw_render.so, include/igw_render.h) ----
-    def _draw(self, stream=None):
-        """What reset / step draw after their launch (renderer='hip'); on the current stream unless one is given."""
-        self._pov.draw(self, stream)
+    def _draw(self, stream=None, restart=None, fill=False, pending=True):
+        """What reset / step draw after their launch (renderer='hip'); on the current stream unless one is given.
+        `restart` / `fill` are the stack's restart rule of this draw (pov_obs; ignored without); pending=False (a
+        capture's draws) leaves the "next draw fills" flag alone."""
+        if pending and self._pov.obs is not None:
+            fill = _take_obs_fill(self) or fill
+        self._pov.draw(self, stream, None, restart, fill)
+
+    def _obs_moved(self):
+        """The state moved without a draw: the next draw restarts every env's stack (pov_obs)."""
+        self._obs_fill = True
+        for e in [self] + self._children:
+            e._obs_fill = True
+        if self._obs_flags is not None:
+            self._obs_flags[0].fill_(1)
+
+    def _obs_device_flags(self):
+        """uint8 [2, N] on the device: row 0 the "next draw fills" flag per env, row 1 a scratch restart mask."""
+        if self._obs_flags is None:
+            self._obs_flags = torch.zeros((2, self.num_envs), dtype=torch.uint8, device=self.device)
+            self._obs_flags[0].fill_(int(self._obs_fill))
+        return self._obs_flags
+
+    def render_pov_obs(self, spec, out=None, restart=None, fill=False, frame=None):
+        """The observation of every env's CURRENT state in the layout `spec` (a render.ObsSpec or a dict), for callers
+        who keep their own stack: one igw_render_pov_obs launch on the current stream that shifts this frame into `out`
+        (the [N, K * planes, H, W] tensor of spec.dtype an earlier call returned), restarting the stack of env i where
+        `restart` (a uint8 / bool device tensor [N], any stride) is not 0, of every env with fill=True.  out=None
+        returns a new, filled tensor; with `out` nothing is allocated, so the call can be captured.  `frame` (uint8
+        [N, H, W, 3]) also receives what render_pov() draws."""
+        spec = R.ObsSpec.of(spec)
+        if restart is not None and not (torch.is_tensor(restart) and restart.dtype in (torch.uint8, torch.bool)):
+            restart = torch.as_tensor(restart, device=self.device).ne(0).to(torch.uint8)
+        return _render_obs_rows(self, spec, out, frame, restart, fill, self._stream())
 
     def set_render_atlas(self, atlas):
         """The texture atlas of render_pov: uint8 [S, S, 4] (numpy or tensor, row 0 = the top image row), S a multiple
@@ -473,7 +534,9 @@ class VecGridWorld:
         exactly as they do eagerly.  What does NOT: the sampler SETTINGS and the episode-log buffers are kernel
         parameters, frozen at capture; after set_task_sampling / set_random_tasks / enable_ / disable_trajectory_log
         replay() raises (capture again).  With renderer='hip' the graph ends with the launch that draws obs['pov'] (and
-        the planes of pov_outputs) of the state after the last step: what the eager loop's last step() leaves there."""
+        the planes of pov_outputs) of the state after the last step: what the eager loop's last step() leaves there.
+        With a pov_obs of stack > 1 the draw follows EVERY step launch of its chain inside the graph (each frame has to
+        enter the stack), with the eager loop's restart rule; replay() returns obs['pov_obs'] too."""
         self._need_tasks()
         return StepGraph(self, actions, record, chains)
 
@@ -488,6 +551,7 @@ class VecGridWorld:
         self._need_tasks()
         L.check(self.lib.igw_rollout_walking(self.ctx, int(T), int(seed), int(t0), int(env_offset),
                                              self._stream()), 'igw_rollout_walking')
+        self._obs_moved()
 
     def rollout_actions(self, actions, return_rewards=False):
         """Fused replay of a recorded action sequence: `actions` int32 [T, N] (Discrete(18) ids), or for the flying action
@@ -529,6 +593,7 @@ class VecGridWorld:
             L.check(self.lib.igw_rollout_walking_actions(self.ctx, a.data_ptr(), int(T), rp, dp, self._stream()),
                     'igw_rollout_walking_actions')
         self._keep = keep  # the launch reads them asynchronously
+        self._obs_moved()
         return (rw, dn) if return_rewards else None
 
     def fill_actions(self, n_steps, seed, t0=0, env_offset=0):
@@ -659,6 +724,11 @@ class StepGraph:
         self.graphs = [self.graph] + [torch.cuda.CUDAGraph() for _ in range(chains - 1)]
         if env._pov is not None:
             env._atlas()   # (allocated before the capture)
+        # a stack of K > 1 frames takes every step's frame: the draw follows each step launch of its chain.  The first
+        # draw of a replay restarts the envs whose "next draw fills" byte is set (device memory, so it holds at replay
+        # time) beside those the eager rule restarts, and clears the bytes.
+        stacked = env._pov is not None and env._pov.obs is not None and env._pov.spec.stack > 1
+        flags = env._obs_device_flags() if stacked else None
         self.streams = [cap] + [torch.cuda.Stream(device=dev) for _ in range(chains - 1)]
         for k in range(chains):
             st = self.streams[k]
@@ -672,8 +742,20 @@ class StepGraph:
                     L.check(fn(ctx, *(p + o for p, o in zip(ptrs[t], offs)), h), 'step (capture)')
                     if record:
                         self.outs[t, lo:lo + n].copy_(env.out_buf[lo:lo + n])
-                if env._pov is not None:   # the frame (and planes) of the state after the last step
-                    (env if chains == 1 else self.subs[k])._draw(h)
+                    if stacked:
+                        e = env if chains == 1 else self.subs[k]
+                        done = env.done[lo:lo + n] if env.autoreset else None
+                        if t == 0:
+                            first, mask = flags[0, lo:lo + n], flags[1, lo:lo + n]
+                            if done is None:
+                                mask.copy_(first)
+                            else:
+                                torch.bitwise_or(done, first, out=mask)
+                            first.zero_()
+                            done = mask
+                        e._draw(h, restart=done, pending=False)
+                if env._pov is not None and not stacked:   # the frame (and planes) of the state after the last step
+                    (env if chains == 1 else self.subs[k])._draw(h, pending=False)
             torch.cuda.current_stream(dev).wait_stream(st)
         if record:
             f = self.outs.view(torch.float32)
@@ -705,6 +787,10 @@ class StepGraph:
                     g.replay()
             for st in self.streams:
                 cur.wait_stream(st)
+        if env._pov is not None and env._pov.obs is not None:   # the graph's first draw took the flag (a stack of one
+            env._obs_fill = False                                # frame has nothing to restart)
+            for c in self.subs or ():
+                c._obs_fill = False
         obs = env._obs.copy()
         return (obs if env._pov is None else env._pov.add_to(obs)), env.reward, env.done, {}
 
@@ -740,6 +826,8 @@ class SubBatch:
         self._pov = None if parent._pov is None else parent._pov.rows(sl)
         self._rows = tuple(t[sl] for t in parent._rows)
         self.pov = self._pov.tensors.get('rgb') if self._pov else None
+        self.pov_obs = self._pov.obs if self._pov else None
+        self.autoreset, self._obs_fill, self._obs_flags = parent.autoreset, parent._obs_fill, None
         self._inherit_sampling()
 
     def _inherit_sampling(self):
@@ -764,11 +852,13 @@ class SubBatch:
     def _stream(self):
         return C.c_void_p(self.stream.cuda_stream)
 
-    def _draw(self, stream=None):
+    def _draw(self, stream=None, restart=None, fill=False, pending=True):
         """What reset / step draw after their launch (renderer='hip'), on this sub-batch's stream unless one is given
-        (a capture's)."""
+        (a capture's); `restart`, `fill` and `pending` as for VecGridWorld._draw."""
         if self._pov is not None:
-            self._pov.draw(self, stream, self.stream)
+            if pending and self._pov.obs is not None:
+                fill = _take_obs_fill(self) or fill
+            self._pov.draw(self, stream, self.stream, restart, fill)
 
     def _atlas(self):
         return self.parent._atlas()
@@ -797,11 +887,11 @@ class SubBatch:
             raise ValueError(f'walking action needs {self.num_envs} entries, got {actions_i32.numel()}')
         actions_i32.record_stream(self.stream)
         L.check(self.lib.igw_step_walking(self.ctx, actions_i32.data_ptr(), self._stream()), 'igw_step_walking')
-        self._draw()
+        self._draw(restart=self.done if self.autoreset else None)
 
     def reset(self):
         L.check(self.lib.igw_reset(self.ctx, None, 0, self._stream()), 'igw_reset')
-        self._draw()
+        self._draw(fill=True)
         return self.obs()
 
     def synchronize(self):
@@ -820,32 +910,49 @@ def _state_obs(e):
 class _Pov:
     """The persistent outputs of renderer='hip': output name -> tensor as pov_outputs names them, for the whole batch
     or, through rows(), for a SubBatch's slice of the same memory.  The default, ('rgb',), is drawn by the plain entry
-    (render.launch with outputs=None); anything else by one _aux launch."""
+    (render.launch with outputs=None); anything else by one _aux launch.  With pov_obs, `obs` is the stack tensor
+    [N, K * planes, H, W] of `spec` and `tensors` holds the frame or nothing (pov_frame=False): one
+    igw_render_pov_obs launch (render.launch_obs) draws both."""
 
-    def __init__(self, tensors):
-        self.tensors = tensors
-        self.plain = tuple(tensors) == ('rgb',)
+    def __init__(self, tensors, spec=None, obs=None):
+        self.tensors, self.spec, self.obs = tensors, spec, obs
+        self.plain = tuple(tensors) == ('rgb',) and obs is None
 
     def rows(self, sl):
-        return _Pov({k: t[sl] for k, t in self.tensors.items()})
+        return _Pov({k: t[sl] for k, t in self.tensors.items()}, self.spec, None if self.obs is None else self.obs[sl])
 
-    def draw(self, env, stream=None, own=None):
+    def draw(self, env, stream=None, own=None, restart=None, fill=False):
         """Draws the tensors from env's state rows on `stream`; without one on the env's own, where the tensors are
-        then marked as in use if that is a side stream, `own` (a SubBatch's)."""
+        then marked as in use if that is a side stream, `own` (a SubBatch's).  `restart` (None or a uint8 tensor [n]
+        at any stride) and `fill` are the stack's restart rule of this draw (igw_render_obs); ignored without pov_obs."""
         if stream is None:
             stream = env._stream()
-            for t in self.tensors.values() if own is not None else ():
+            for t in (*self.tensors.values(), *(() if self.obs is None else (self.obs,))) if own is not None else ():
                 t.record_stream(own)
-        if self.plain:
+        if self.obs is not None:
+            _render_obs_rows(env, self.spec, self.obs, self.tensors.get('rgb'), restart, fill, stream)
+        elif self.plain:
             _render_rows(env, self.tensors['rgb'], 3, None, None, stream)
         else:
             _render_rows(env, self.tensors, 3, None, tuple(self.tensors), stream)
 
     def add_to(self, obs):
-        """Adds the tensors to an observation dict, 'rgb' as 'pov' and the planes under their names; returns it."""
+        """Adds the tensors to an observation dict, 'rgb' as 'pov', the planes under their names and the stack as
+        'pov_obs'; returns it."""
         for k, t in self.tensors.items():
             obs['pov' if k == 'rgb' else k] = t
+        if self.obs is not None:
+            obs['pov_obs'] = self.obs
         return obs
+
+
+def _take_obs_fill(env):
+    """Whether the draw that is about to be launched for `env` (a VecGridWorld or a SubBatch) restarts every stack
+    because the state moved without a draw; clears the flag, on the device too where a graph reads it."""
+    fill, env._obs_fill = env._obs_fill, False
+    if fill and env._obs_flags is not None:
+        env._obs_flags[0].zero_()
+    return fill
 
 
 def _render_rows(env, out, channels, size, outputs, stream, alloc_stream=None):
@@ -855,6 +962,14 @@ def _render_rows(env, out, channels, size, outputs, stream, alloc_stream=None):
     return R.launch('pov', (agent.data_ptr(), grid.data_ptr(), occ.data_ptr(), n), n,
                     size if size is not None else env.render_size, channels, outputs, out, env._atlas(), env.device,
                     stream, alloc_stream)
+
+
+def _render_obs_rows(env, spec, out, frame, restart, fill, stream, alloc_stream=None):
+    """One igw_render_pov_obs launch (render.launch_obs) over the state rows of a whole VecGridWorld or of a SubBatch."""
+    agent, grid, occ = env._rows
+    n = env.num_envs
+    return R.launch_obs((agent.data_ptr(), grid.data_ptr(), occ.data_ptr(), n), n, env.render_size, spec, out, frame,
+                        restart, fill, env._atlas(), env.device, stream, alloc_stream)
 
 
 def task_eval(targets, grids, full_grids=None, invariant=None, device='cuda:0'):
