@@ -15,3 +15,5 @@ from .visualizer import Visualizer, look_at, orbit_poses, render_views  # noqa: 
 from .render import ObsSpec, decode_surface, unproject  # noqa: F401,E402
 from . import codec  # noqa: F401,E402
 from .codec import encode_jpeg, jpeg_bytes  # noqa: F401,E402
+from . import query  # noqa: F401,E402
+from .query import ACTION_NAMES as action_mask_names  # noqa: F401,E402

@@ -367,6 +367,11 @@ class GridWorld:
             reward = right * self.right_placement_scale
         return obs, reward, bool(self._host['out'][52]), {}
 
+    def action_mask(self):
+        """np.bool_ [18]: which Discrete(18) actions would act on the state of the last reset / step
+        (VecGridWorld.action_mask).  ValueError for the flying and Dict action spaces."""
+        return self._vec.action_mask()[0].cpu().numpy().astype(np.bool_)
+
     def render(self):
         """Renderer.render() (gridworld/render.py:129-144): the current frame as RGBA uint8 [H, W, 4], row 0 on top."""
         if not self._renders():

@@ -12,6 +12,7 @@ import torch
 
 from . import _lib as L
 from . import codec as K
+from . import query as Q
 from . import render as R
 
 
@@ -39,7 +40,7 @@ class VecGridWorld:
                  size_reward=True, max_steps=250, right_placement_scale=1., wrong_placement_scale=0.1,
                  discretize=True, autoreset=False, num_tasks=None, lanes_per_env=0, debug_flags=0, env_index_base=0,
                  host_records=False, render=False, render_size=(64, 64), target_in_obs=False, vector_state=True, name='', fake=False,
-                 renderer=None, pov_outputs=('rgb',), pov_obs=None, pov_frame=True):
+                 renderer=None, pov_outputs=('rgb',), pov_obs=None, pov_frame=True, action_mask=False):
         """create_env's keyword arguments (gridworld/env.py:333-338) plus the batch's own: num_envs, device,
         autoreset (reset inside step), num_tasks (rows of the task table, default num_envs), lanes_per_env
         (0 = automatic), env_index_base (global index of env 0: rank / sub-batch offset), debug_flags (IGW_DIAG
@@ -63,7 +64,10 @@ class VecGridWorld:
         frame drawn then already shows the next episode), step() with autoreset=False none (the terminal frame joins
         its own episode's stack); after anything that moves the state without drawing (rollout, rollout_actions,
         load_state_dict, set_tasks) the next draw fills.  pov_frame=False (only with pov_obs) drops obs['pov'] and its
-        store.  pov_obs goes with pov_outputs=('rgb',) only."""
+        store.  pov_obs goes with pov_outputs=('rgb',) only.
+        action_mask=True (Discrete(18) walking only) adds obs['action_mask'], a persistent uint8 [N, 18] tensor: which
+        actions would act on the state the observation shows (action_mask()), written by one
+        igw_action_mask launch on the same stream after the step / reset launch (and after the draw)."""
         if renderer not in (None, 'hip'):
             raise ValueError(f"unknown renderer {renderer!r}; the one renderer is 'hip'")
         pov_outputs = R.check_outputs(pov_outputs)
@@ -84,6 +88,8 @@ class VecGridWorld:
             raise L.IgwError('VecGridWorld needs a HIP device (no CPU fallback)')
         if action_space not in ('walking', 'flying'):
             raise ValueError(f'unknown action_space {action_space!r}')
+        if action_mask and (action_space != 'walking' or not discretize):
+            raise ValueError('action_mask=True needs the Discrete(18) walking action space')
         self.lib = L.load()
         self.device = torch.device(device)
         self.num_envs = int(num_envs)
@@ -92,6 +98,7 @@ class VecGridWorld:
         self.walk_dict = action_space == 'walking' and not discretize
         self.max_steps = int(max_steps)
         self.autoreset = bool(autoreset)
+        self.select_and_place = bool(select_and_place)
         N, T, dev = self.num_envs, self.num_tasks, self.device
         z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
         # What a host-side consumer reads back after a step -- output, agent and aux records, the grid -- comes from ONE
@@ -158,6 +165,11 @@ class VecGridWorld:
         self._rows = (self.agent_buf, self.grid_buf, self.occ_buf)   # the state a frame is drawn from
         self.pov = self._pov.tensors.get('rgb') if self._pov else None
         self.pov_obs = self._pov.obs if self._pov else None
+        # obs['action_mask'] (action_mask=True): rewritten by every reset / step, and by whatever else moves the state
+        self._mask = None
+        if action_mask:
+            Q.load()   # (built before the first step, not inside it)
+            self._mask = self._obs['action_mask'] = z((N, Q.ACTIONS), torch.uint8)
 
     def __del__(self):
         ctx = getattr(self, 'ctx', None)
@@ -326,6 +338,7 @@ class VecGridWorld:
             getattr(self, k).copy_(state[k])
         self._have_tasks = True
         self._obs_moved()
+        self._mask_moved()
 
     # ---- reset / step ----
     def _need_tasks(self):
@@ -354,6 +367,8 @@ class VecGridWorld:
         if self._pov is not None:
             self._draw(restart=None if m is None else m.reshape(-1), fill=m is None)
             self._pov.add_to(obs)
+        if self._mask is not None:
+            _mask_rows(self, self._mask, False, None, self._stream())
         return obs
 
     @staticmethod
@@ -398,6 +413,8 @@ class VecGridWorld:
         if self._pov is not None:
             self._draw(restart=self.done if self.autoreset else None)
             self._pov.add_to(obs)
+        if self._mask is not None:
+            _mask_rows(self, self._mask, False, None, self._stream())
         return obs, self.reward, self.done, {}
 
     def _step_dict(self, actions, N):
@@ -434,6 +451,26 @@ class VecGridWorld:
             if rc:
                 L.check(rc, 'igw_step_flying')
             self._act_keep = (mv, cam, inv, pl)
+
+    # ---- which actions would act (libigw_query.so, include/igw_query.h) ----
+    def action_mask(self, out=None, look=False, sample=None):
+        """Which of the 18 walking actions would act on every env's CURRENT state (after a step that ended an episode of
+        an auto-reset env: the new episode's): uint8 [N, 18], 1 where the action would do something -- the place / break
+        / hotbar actions would change the grid, a jump would start, the pitch would move; the no-op, the moves and the
+        yaw actions are always 1 (names in query.ACTION_NAMES).  One igw_action_mask launch on the
+        current stream; with `out` (a contiguous uint8 device tensor of that shape) nothing is allocated, so the call
+        can be captured.  look=True also returns int16 [N, 2]: the grid cell (index into the flat [9 * 11 * 11] grid)
+        that action 16 would clear and the one action 17 would fill, -1 where they would do nothing.  sample=(seed, t)
+        also returns int32 [N]: one action per env drawn uniformly from the set bits of its mask, a counter RNG keyed by
+        (seed, global env index, t) (include/igw_query.h) -- a masked random policy without a host round trip.  The
+        result is the mask alone or the tuple (mask, look, actions) of what was asked for; with look / sample `out` may
+        be the tuple of tensors to write.  Discrete(18) walking only: ValueError for flying and Dict-action envs."""
+        return _mask_rows(self, out, look, sample, self._stream())
+
+    def _mask_moved(self):
+        """The state moved without a step (a fused rollout, load_state_dict): obs['action_mask'] follows it."""
+        if self._mask is not None:
+            _mask_rows(self, self._mask, False, None, self._stream())
 
     # ---- first-person frames (libigw_render.so, include/igw_render.h) ----
     def _draw(self, stream=None, restart=None, fill=False, pending=True):
@@ -541,10 +578,13 @@ class VecGridWorld:
         return StepGraph(self, actions, record, chains)
 
     def step_walking_ptr(self, actions_i32):
-        """Hot-loop variant: `actions_i32` is already a contiguous int32 device tensor [N]."""
+        """Hot-loop variant: `actions_i32` is already a contiguous int32 device tensor [N].  It launches the step and,
+        with action_mask=True, the mask (obs['action_mask'] follows the state); it does NOT draw: obs['pov'] and the
+        other render outputs keep what the last step() / reset() left."""
         if actions_i32.numel() != self.num_envs:
             raise ValueError(f'walking action needs {self.num_envs} entries, got {actions_i32.numel()}')
         L.check(self.lib.igw_step_walking(self.ctx, actions_i32.data_ptr(), self._stream()), 'igw_step_walking')
+        self._mask_moved()
 
     def rollout(self, T, seed, t0=0, env_offset=0):
         """T fused walking steps per env with counter-RNG actions and auto-reset (one launch)."""
@@ -552,6 +592,7 @@ class VecGridWorld:
         L.check(self.lib.igw_rollout_walking(self.ctx, int(T), int(seed), int(t0), int(env_offset),
                                              self._stream()), 'igw_rollout_walking')
         self._obs_moved()
+        self._mask_moved()
 
     def rollout_actions(self, actions, return_rewards=False):
         """Fused replay of a recorded action sequence: `actions` int32 [T, N] (Discrete(18) ids), or for the flying action
@@ -594,6 +635,7 @@ class VecGridWorld:
                     'igw_rollout_walking_actions')
         self._keep = keep  # the launch reads them asynchronously
         self._obs_moved()
+        self._mask_moved()
         return (rw, dn) if return_rewards else None
 
     def fill_actions(self, n_steps, seed, t0=0, env_offset=0):
@@ -754,6 +796,9 @@ class StepGraph:
                             first.zero_()
                             done = mask
                         e._draw(h, restart=done, pending=False)
+                    if env._mask is not None:   # obs['action_mask'] follows every step of its chain
+                        e = env if chains == 1 else self.subs[k]
+                        _mask_rows(e, e._mask, False, None, h)
                 if env._pov is not None and not stacked:   # the frame (and planes) of the state after the last step
                     (env if chains == 1 else self.subs[k])._draw(h, pending=False)
             torch.cuda.current_stream(dev).wait_stream(st)
@@ -828,6 +873,9 @@ class SubBatch:
         self.pov = self._pov.tensors.get('rgb') if self._pov else None
         self.pov_obs = self._pov.obs if self._pov else None
         self.autoreset, self._obs_fill, self._obs_flags = parent.autoreset, parent._obs_fill, None
+        self.flying, self.walk_dict, self.select_and_place = parent.flying, parent.walk_dict, parent.select_and_place
+        self.env_index_base = cfg.env_index_base
+        self._mask = None if parent._mask is None else parent._mask[sl]
         self._inherit_sampling()
 
     def _inherit_sampling(self):
@@ -847,7 +895,23 @@ class SubBatch:
 
     def obs(self):
         o = _state_obs(self)
+        if self._mask is not None:
+            o['action_mask'] = self._mask
         return o if self._pov is None else self._pov.add_to(o)
+
+    def action_mask(self, out=None, look=False, sample=None):
+        """VecGridWorld.action_mask for this sub-batch's rows, on its own stream."""
+        for t in out if isinstance(out, (tuple, list)) else (out,):
+            if torch.is_tensor(t):
+                t.record_stream(self.stream)
+        res = _mask_rows(self, out, look, sample, self._stream(), self.stream)
+        for t in res if isinstance(res, tuple) else (res,):
+            t.record_stream(self.stream)
+        return res
+
+    def _mask_moved(self):
+        if self._mask is not None:
+            _mask_rows(self, self._mask, False, None, self._stream())
 
     def _stream(self):
         return C.c_void_p(self.stream.cuda_stream)
@@ -888,10 +952,12 @@ class SubBatch:
         actions_i32.record_stream(self.stream)
         L.check(self.lib.igw_step_walking(self.ctx, actions_i32.data_ptr(), self._stream()), 'igw_step_walking')
         self._draw(restart=self.done if self.autoreset else None)
+        self._mask_moved()
 
     def reset(self):
         L.check(self.lib.igw_reset(self.ctx, None, 0, self._stream()), 'igw_reset')
         self._draw(fill=True)
+        self._mask_moved()
         return self.obs()
 
     def synchronize(self):
@@ -970,6 +1036,16 @@ def _render_obs_rows(env, spec, out, frame, restart, fill, stream, alloc_stream=
     n = env.num_envs
     return R.launch_obs((agent.data_ptr(), grid.data_ptr(), occ.data_ptr(), n), n, env.render_size, spec, out, frame,
                         restart, fill, env._atlas(), env.device, stream, alloc_stream)
+
+
+def _mask_rows(env, out, look, sample, stream, alloc_stream=None):
+    """One igw_action_mask launch (query.launch) over the state rows of a whole VecGridWorld or of a SubBatch."""
+    if env.flying or env.walk_dict:
+        raise ValueError('action_mask is defined for the Discrete(18) walking action space only (the flying and Dict '
+                         'actions turn the camera in the same step as they place)')
+    agent, _, occ = env._rows
+    return Q.launch(agent, occ, env.num_envs, env.select_and_place, out, look, sample, env.env_index_base, env.device,
+                    stream, alloc_stream)
 
 
 def task_eval(targets, grids, full_grids=None, invariant=None, device='cuda:0'):
