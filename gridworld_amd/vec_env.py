@@ -6,6 +6,7 @@ Mirrors the reference's env protocol for render=False / vector_state=True
 gridworld/env.py:333-338.  Observations are tensor views of the state, not copies.
 """
 import ctypes as C
+import weakref
 
 import numpy as np
 import torch
@@ -33,7 +34,271 @@ def _as_rows(x, device, n=None):
     return out
 
 
-class VecGridWorld:
+def _invariant(x, n, device):
+    """The `invariant` argument of a task (a bool or [n]) -> uint8 tensor [n] on device, None as it is."""
+    if x is None:
+        return None
+    return torch.as_tensor(np.broadcast_to(np.asarray(x, dtype=np.uint8), (n,)).copy(), device=device)
+
+
+class _Space:
+    """The layout of one action space, stated here and nowhere else: the C entry that steps it, the entry of its fused
+    action rollout (None: it has none), and per action buffer the dict key (None: the action IS the one tensor), the
+    kernel's dtype and the per-env shape.  The entries take the buffers' pointers in this order."""
+
+    def __init__(self, name, step, rollout, *buffers):
+        self.name, self.step, self.rollout, self.buffers = name, step, rollout, buffers
+        self.counts = tuple(int(np.prod(shape, dtype=np.int64)) for _, _, shape in buffers)   # elements per env
+        self.row_bytes = tuple(dt.itemsize * n for (_, dt, _), n in zip(buffers, self.counts))
+
+    def mismatch(self, who, N, key, x, lead=''):
+        """The one error for a buffer that does not fit the layout (`lead`: 'T' for [T, N, ...] sequences)."""
+        layout = ', '.join(f'{k or "actions"} {dt} [{", ".join(map(str, (*lead, N, *shape)))}]'
+                           for k, dt, shape in self.buffers)
+        return ValueError(f'{who}: the {self.name} action space takes {layout}, got {key or "actions"} {tuple(x.shape)}')
+
+
+_SPACES = {
+    L.WALKING_DISCRETE: _Space('walking', 'igw_step_walking', 'igw_rollout_walking_actions', (None, torch.int32, ())),
+    L.WALKING_DICT: _Space('walking Dict', 'igw_step_walking_dict', None,
+                           ('buttons', torch.uint8, (8,)), ('camera', torch.float32, (2,))),
+    L.FLYING: _Space('flying', 'igw_step_flying', 'igw_rollout_flying_actions',
+                     ('movement', torch.float32, (3,)), ('camera', torch.float32, (2,)),
+                     ('inventory', torch.int32, ()), ('placement', torch.int32, ())),
+}
+BUTTONS = ('forward', 'back', 'left', 'right', 'jump', 'attack', 'use', 'hotbar')   # the reference's keys, env.py:60-70
+# the fields of L.Buffers in their order (the per-env ones are bound by row range), without `stats`
+_ROW_BUFFERS = ('grid_buf', 'occ_buf', 'hist_buf', 'agent_buf', 'aux_buf')
+_TASK_BUFFERS = ('task_target', 'task_start', 'task_start_occ', 'task_meta', 'task_index')
+
+
+class _FillFlag:
+    """"The next draw restarts the stack" (pov_obs): ONE holder per batch, on the VecGridWorld; its sub-batches and the
+    device reach it through here.  The fact is kept per row range that draws (the whole batch, each sub-batch): `drawn`
+    holds the ranges that have drawn since the state last moved without a draw, so the first draw of EACH range after
+    such a move fills.  raise_() -- whatever moved the state without drawing; take() -- an eager draw of a range;
+    captured() -- the first draw of a captured chain, which cannot read the host at replay time: from the first capture
+    on the flag is also one byte per env on the device (row 0 of `dev`; row 1 is the restart mask the captured draw
+    reads).  The bytes are lowered by the whole batch's draws and by replays, not by a sub-batch's eager draw (which
+    launches nothing but its draw on its stream)."""
+
+    def __init__(self, n, device):
+        self.drawn, self.dev, self.n, self.device = weakref.WeakSet(), None, n, device
+
+    def raise_(self):
+        self.drawn.clear()
+        if self.dev is not None:
+            self.dev[0].fill_(1)
+
+    def take(self, rows):
+        """Whether the eager draw of the range `rows` that is about to be launched fills; lowers its flag."""
+        fill = rows not in self.drawn
+        if fill:
+            self.lowered(rows)
+            if rows.parent is None and self.dev is not None:
+                self.dev[0].zero_()
+        return fill
+
+    def lowered(self, *ranges):
+        """These ranges need no fill: a replayed graph's first draws took their flags; a new sub-batch of a batch
+        that has drawn."""
+        self.drawn.update(ranges)
+
+    def on_device(self, root):
+        """(Before a capture: nothing may be allocated inside one.)"""
+        if self.dev is None:
+            self.dev = torch.zeros((2, self.n), dtype=torch.uint8, device=self.device)
+            self.dev[0].fill_(int(root not in self.drawn))
+
+    def captured(self, sl, restart):
+        """The captured form of take(): the restart mask of a replay's first draw of rows `sl` -- the eager rule's
+        `restart` (a uint8 tensor or None) OR the flag bytes as they are at replay time -- computed and the bytes
+        lowered by launches that are captured with the draw."""
+        first, mask = self.dev[0, sl], self.dev[1, sl]
+        if restart is None:
+            mask.copy_(first)
+        else:
+            torch.bitwise_or(restart, first, out=mask)
+        first.zero_()
+        return mask
+
+
+class _Rows:
+    """Rows [lo, lo + n) of a batch's state behind one igw context, and what follows that state: the base of
+    VecGridWorld (every row, launches on the current stream) and SubBatch (a slice of its parent's tensors, launches on
+    a stream of its own).  The two differ by `parent`, `lo` and `stream` alone."""
+    parent, lo, stream = None, 0, None
+
+    def _root(self):
+        return self if self.parent is None else self.parent
+
+    def _open(self, cfg, stats_buf):
+        """Creates the context of `cfg` over this row range of the root's buffers."""
+        root, sl = self._root(), slice(self.lo, self.lo + cfg.num_envs)
+        self.cfg, self.num_envs, self.env_index_base, self.stats_buf = cfg, cfg.num_envs, cfg.env_index_base, stats_buf
+        self.ctx = C.c_void_p()
+        L.check(self.lib.igw_create(C.byref(cfg), C.byref(self.ctx)), 'igw_create')
+        bound = [getattr(root, k)[sl] for k in _ROW_BUFFERS] + [getattr(root, k) for k in _TASK_BUFFERS] + \
+            [root.out_buf[sl], stats_buf]
+        L.check(self.lib.igw_bind_buffers(self.ctx, C.byref(L.Buffers(*[t.data_ptr() for t in bound]))),
+                'igw_bind_buffers')
+        self._sl = sl
+        self._rows = (root.agent_buf[sl], root.grid_buf[sl], root.occ_buf[sl])   # the state a frame is drawn from
+
+    def _follow_with(self, pov, mask):
+        """The persistent tensors that follow the state (a _Pov or None; obs['action_mask'] or None): this range's
+        rows of them, and the observation dict that holds them beside the state's views."""
+        self._pov, self._mask = pov, mask
+        self.pov = pov.tensors.get('rgb') if pov else None
+        self.pov_obs = pov.obs if pov else None
+        self._obs = {'agentPos': self.agent_pos, 'inventory': self.inventory, 'compass': self.compass.unsqueeze(1),
+                     'grid': self.grid}
+        if pov is not None:
+            pov.add_to(self._obs)
+        if mask is not None:
+            self._obs['action_mask'] = mask
+
+    def __del__(self):
+        ctx = getattr(self, 'ctx', None)
+        if ctx:
+            self.lib.igw_destroy(ctx)
+            self.ctx = None
+
+    def _stream(self):
+        if self.stream is None:
+            return C.c_void_p(torch._C._cuda_getCurrentRawStream(self._dev_index))
+        return C.c_void_p(self.stream.cuda_stream)
+
+    def _in_use(self, *tensors):
+        """Marks tensors as in use on the range's own stream, so that the caching allocator does not recycle them while
+        a launch there reads or writes them; on the current stream there is nothing to mark."""
+        if self.stream is not None:
+            for t in tensors:
+                if torch.is_tensor(t):
+                    t.record_stream(self.stream)
+
+    def _atlas(self):
+        root = self._root()
+        if root._render_atlas is None:
+            root.set_render_atlas(None)
+        return root._render_atlas
+
+    def obs(self):
+        return self._obs.copy()
+
+    # ---- what follows a launch ----
+    def _follow(self, restart=None, fill=False, draw=True):
+        """The ONE path after a launch that moved this range's state: the draw (renderer='hip'), then the action mask
+        (action_mask=True), on the range's stream.  `restart` / `fill` are the stack's restart rule of the draw
+        (pov_obs; ignored without): a uint8 tensor [n] of the rows to restart -- a step's _ended(), reset(mask)'s
+        mask -- or fill=True for every row (a full reset); the range's first draw after an undrawn move fills too.
+        draw=False is the move that draws nothing (the fused rollouts, load_state_dict): it raises that flag."""
+        if not draw:
+            self._root()._fill.raise_()
+        elif self._pov is not None:
+            if self._pov.obs is not None:
+                fill = self._root()._fill.take(self) or fill
+            self._draw(None, restart, fill)
+        self._follow_mask()
+
+    def _follow_captured(self, stream, first, last):
+        """_follow() after a step inside a captured chain, on the capture's stream (`first` / `last`: of the chain's
+        steps).  A stack of K > 1 frames takes every step's frame, so the draw follows each step, the first with the
+        captured form of the restart rule (_FillFlag.captured); otherwise one draw follows the last step's mask --
+        what the eager loop's last step() leaves."""
+        pov = self._pov
+        if pov is not None and pov.stacked:
+            restart = self._ended()
+            self._draw(stream, self._root()._fill.captured(self._sl, restart) if first else restart)
+        self._follow_mask(stream)
+        if last and pov is not None and not pov.stacked:
+            self._draw(stream)
+
+    def _follow_mask(self, stream=None):
+        if self._mask is not None:
+            _mask_rows(self, self._mask, False, None, self._stream() if stream is None else stream)
+
+    def _ended(self):
+        """The stacks a step's draw restarts: those of the envs whose episode just ended if they auto-reset (the frame
+        then shows the next episode), none otherwise (the terminal frame joins its own episode's stack)."""
+        return self.done if self.autoreset else None
+
+    def _draw(self, stream=None, restart=None, fill=False):
+        """Draws the persistent outputs from this range's state rows on `stream` (a capture's); without one on the
+        range's own, where the tensors are then marked as in use.  `restart` (None or a uint8 tensor [n] at any
+        stride) and `fill` go to igw_render_pov_obs; ignored without pov_obs."""
+        pov = self._pov
+        if stream is None:
+            stream = self._stream()
+            self._in_use(*pov.tensors.values(), pov.obs)
+        if pov.obs is not None:
+            _render_obs_rows(self, pov.spec, pov.obs, pov.tensors.get('rgb'), restart, fill, stream)
+        elif pov.plain:
+            _render_rows(self, pov.tensors['rgb'], 3, None, None, stream)
+        else:
+            _render_rows(self, pov.tensors, 3, None, tuple(pov.tensors), stream)
+
+    def step_walking_ptr(self, actions_i32):
+        """Hot-loop variant: `actions_i32` is already a contiguous int32 device tensor [n], launched on the range's
+        stream (on a stream of its own the tensor is marked as in use there).  With action_mask=True the mask follows.
+        The WHOLE batch's call does NOT draw: obs['pov'] and the other render outputs keep what the last step() /
+        reset() left; a SubBatch's draws, as step() does."""
+        if actions_i32.numel() != self.num_envs:
+            raise _SPACES[L.WALKING_DISCRETE].mismatch('step_walking_ptr', self.num_envs, None, actions_i32)
+        self._in_use(actions_i32)
+        L.check(self.lib.igw_step_walking(self.ctx, actions_i32.data_ptr(), self._stream()), 'igw_step_walking')
+        # The one asymmetry between the two classes, decided here: a sub-batch has no step() of its own, so this is
+        # its step and it draws; the whole batch's never drew (and, not being an undrawn MOVE of the episode
+        # boundaries, it leaves the stacks' fill flag alone): its callers draw when they want a frame.
+        if self.parent is None:
+            self._follow_mask()
+        else:
+            self._follow(self._ended())
+
+    # ---- which actions would act (libigw_query.so, include/igw_query.h) ----
+    def action_mask(self, out=None, look=False, sample=None):
+        """Which of the 18 walking actions would act on every env's CURRENT state (after a step that ended an episode of
+        an auto-reset env: the new episode's): uint8 [N, 18], 1 where the action would do something -- the place / break
+        / hotbar actions would change the grid, a jump would start, the pitch would move; the no-op, the moves and the
+        yaw actions are always 1 (DESIGN.md section 10; names in query.ACTION_NAMES).  One igw_action_mask launch on the
+        range's stream (a VecGridWorld's: the current one; a SubBatch's: its own, for its rows); with `out` (a
+        contiguous uint8 device tensor of that shape) nothing is allocated, so the call
+        can be captured.  look=True also returns int16 [N, 2]: the grid cell (index into the flat [9 * 11 * 11] grid)
+        that action 16 would clear and the one action 17 would fill, -1 where they would do nothing.  sample=(seed, t)
+        also returns int32 [N]: one action per env drawn uniformly from the set bits of its mask, a counter RNG keyed by
+        (seed, global env index, t) (include/igw_query.h) -- a masked random policy without a host round trip.  The
+        result is the mask alone or the tuple (mask, look, actions) of what was asked for; with look / sample `out` may
+        be the tuple of tensors to write.  Discrete(18) walking only: ValueError for flying and Dict-action envs."""
+        self._in_use(*(out if isinstance(out, (tuple, list)) else (out,)))
+        res = _mask_rows(self, out, look, sample, self._stream(), self.stream)
+        self._in_use(*(res if isinstance(res, tuple) else (res,)))
+        return res
+
+    # ---- first-person frames (libigw_render.so, include/igw_render.h) ----
+    def render_pov(self, out=None, channels=3, size=None, outputs=None, codec=None, quality=90):
+        """The first-person frame of every env's CURRENT state (see _make_views for auto-reset envs): uint8
+        [N, H, W, channels] with W, H = size (default render_size), row 0 the top image row, channels 3 (RGB) or 4 (RGBA,
+        what the reference's Renderer.render() returns).  One launch on the range's stream (a VecGridWorld's: the
+        current one; a SubBatch's: its own, for its rows); with `out` (a contiguous
+        uint8 device tensor of that shape) nothing is allocated, so the call can be captured in a graph.
+        outputs (a tuple of 'rgb', 'depth', 'label', 'surface') returns a dict name -> tensor instead, from one
+        igw_render_pov_aux launch: the frame and / or the [N, H, W] planes float32 depth, uint8 label, int16 surface
+        (include/igw_render.h); `out` is then a dict of preallocated tensors under those names, or None.
+        codec='jpeg' returns (buf, sizes) of codec.encode_jpeg instead: the frames are drawn, then encoded at `quality`
+        by a second launch on the same stream; `out` is then the (buf, sizes) pair to encode into, or None."""
+        self._in_use(*(out.values() if isinstance(out, dict) else out if isinstance(out, (tuple, list)) else (out,)))
+
+        def draw(out=None, outputs=None):
+            return _render_rows(self, out, channels, size, outputs, self._stream(), self.stream)
+        with torch.cuda.stream(self.stream):
+            res = K.encoded(codec, outputs, quality, out, draw)
+        if res is None:
+            return draw(out, outputs)
+        self._in_use(*res)
+        return res
+
+
+class VecGridWorld(_Rows):
     """N envs on one GPU.  kwargs follow create_env (gridworld/env.py:333-338)."""
 
     def __init__(self, num_envs, device='cuda:0', action_space='walking', select_and_place=True,
@@ -96,6 +361,8 @@ class VecGridWorld:
         self.num_tasks = int(num_tasks or num_envs)
         self.flying = action_space == 'flying'
         self.walk_dict = action_space == 'walking' and not discretize
+        mode = L.FLYING if self.flying else L.WALKING_DICT if self.walk_dict else L.WALKING_DISCRETE
+        self._space = _SPACES[mode]
         self.max_steps = int(max_steps)
         self.autoreset = bool(autoreset)
         self.select_and_place = bool(select_and_place)
@@ -121,23 +388,14 @@ class VecGridWorld:
         self.task_start_occ = z((T, L.OCC_WORDS), torch.int32)
         self.task_meta = z((T, L.TASK_META_BYTES), torch.uint8)
         self.task_index = z((T, L.TASK_INDEX_BYTES), torch.uint8)   # colour index of the synthetic targets (include/igw.h)
-        self.stats_buf = z((L.STAT_STRIPES, 8), torch.int64)
         self._make_views()
         # Agent.__init__ (core/world.py:12-29): time_int_steps = 2, active_block = BLUE, inventory 20
         self.agent_buf.view(torch.int16)[:, 24:30] = 20
         self.agent_buf[:, 62] = 1 << 2  # u16 pack: time_int_steps code 0 (= 2), active_block 1
-        self.cfg = L.Config(dev.index or 0, N, T,
-                            L.FLYING if self.flying else L.WALKING_DICT if self.walk_dict else L.WALKING_DISCRETE,
-                            int(select_and_place), int(size_reward), self.max_steps, int(autoreset),
-                            float(right_placement_scale), float(wrong_placement_scale), int(lanes_per_env),
-                            int(debug_flags), int(env_index_base))
-        self.env_index_base = int(env_index_base)
-        self.ctx = C.c_void_p()
-        L.check(self.lib.igw_create(C.byref(self.cfg), C.byref(self.ctx)), 'igw_create')
-        b = L.Buffers(*[t.data_ptr() for t in (self.grid_buf, self.occ_buf, self.hist_buf, self.agent_buf, self.aux_buf,
-                                                self.task_target, self.task_start, self.task_start_occ, self.task_meta,
-                                                self.task_index, self.out_buf, self.stats_buf)])
-        L.check(self.lib.igw_bind_buffers(self.ctx, C.byref(b)), 'igw_bind_buffers')
+        self._open(L.Config(dev.index or 0, N, T, mode, int(select_and_place), int(size_reward), self.max_steps,
+                            int(autoreset), float(right_placement_scale), float(wrong_placement_scale),
+                            int(lanes_per_env), int(debug_flags), int(env_index_base)),
+                   z((L.STAT_STRIPES, 8), torch.int64))
         self.user_target = None
         self._have_tasks = False
         self._tasks_filled = 0       # rows of the task table written so far (what task sampling draws from)
@@ -151,31 +409,19 @@ class VecGridWorld:
         self._render_atlas = None
         # what reset / step draw (renderer='hip'): the persistent tensors of pov_outputs; pov is obs['pov'], [N, H, W, 3]
         self.pov_outputs = pov_outputs if renderer == 'hip' else ()
-        self._pov = None
+        pov = None
         if renderer == 'hip' and pov_obs is None:
-            self._pov = _Pov(R.targets(N, self.render_size, 3, pov_outputs, None, dev)[0])
+            pov = _Pov(R.targets(N, self.render_size, 3, pov_outputs, None, dev)[0])
         elif renderer == 'hip':   # the stack, and the frame unless pov_frame=False: one igw_render_pov_obs launch
             W, H = self.render_size
             frame = {'rgb': R.targets(N, self.render_size, 3, None, None, dev)[0]} if pov_frame else {}
-            self._pov = _Pov(frame, pov_obs, torch.zeros(pov_obs.shape(N, (W, H)), dtype=pov_obs.dtype, device=dev))
+            pov = _Pov(frame, pov_obs, torch.zeros(pov_obs.shape(N, (W, H)), dtype=pov_obs.dtype, device=dev))
         self.pov_obs_spec = pov_obs
-        # the next draw restarts every env's stack: set by whatever moves the state without drawing.  _obs_flags are
-        # the same flag and a scratch mask as device bytes per env, for draws inside a captured graph (StepGraph).
-        self._obs_fill, self._obs_flags = True, None
-        self._rows = (self.agent_buf, self.grid_buf, self.occ_buf)   # the state a frame is drawn from
-        self.pov = self._pov.tensors.get('rgb') if self._pov else None
-        self.pov_obs = self._pov.obs if self._pov else None
-        # obs['action_mask'] (action_mask=True): rewritten by every reset / step, and by whatever else moves the state
-        self._mask = None
+        self._fill = _FillFlag(N, dev)   # raised: the first draw fills
         if action_mask:
             Q.load()   # (built before the first step, not inside it)
-            self._mask = self._obs['action_mask'] = z((N, Q.ACTIONS), torch.uint8)
-
-    def __del__(self):
-        ctx = getattr(self, 'ctx', None)
-        if ctx:
-            self.lib.igw_destroy(ctx)
-            self.ctx = None
+        # obs['action_mask'] (action_mask=True): rewritten by every reset / step, and by whatever else moves the state
+        self._follow_with(pov, z((N, Q.ACTIONS), torch.uint8) if action_mask else None)
 
     def _make_views(self):
         """The observation / result tensors of the env protocol (env.py:281-303) and the per-env task row / episode
@@ -198,11 +444,7 @@ class VecGridWorld:
         self.env_task = a[:, 2]                       # row of the task table
         self.episode = a[:, 3]                        # episodes started (keys the device-side task generators)
         self.grid = torch.as_strided(self.grid_buf, (N, 9, 11, 11), (L.GRID_STRIDE, 121, 11, 1))
-        self._obs = _state_obs(self)
         self._dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
-
-    def _stream(self):
-        return C.c_void_p(torch._C._cuda_getCurrentRawStream(self._dev_index))
 
     # ---- tasks (GridWorld.set_task / Task.__init__ / initialize_world) ----
     def set_tasks(self, targets, starts=None, full_grids=None, invariant=None, init_pose=None,
@@ -214,9 +456,7 @@ class VecGridWorld:
         T = tgt.shape[0]
         st = _as_rows(starts, dev)
         fg = _as_rows(full_grids, dev)
-        inv = None
-        if invariant is not None:
-            inv = torch.as_tensor(np.broadcast_to(np.asarray(invariant, dtype=np.uint8), (T,)).copy(), device=dev)
+        inv = _invariant(invariant, T, dev)
         for name, g, hi in (('targets', tgt, 7), ('starts', st, 6), ('full_grids', fg, 7)):
             # block ids are 0..7 (the observation space's range, env.py:85); a starting block is taken off the inventory
             # of its colour, ids 1..6 (env.py:243-246: the reference raises IndexError for 7).  The C ABI counts
@@ -257,7 +497,7 @@ class VecGridWorld:
                 self.env_task.zero_()
         self._keep = (tgt, st, fg, inv, pose)  # keep inputs alive until the async kernel ran
         self._have_tasks = True
-        self._obs_moved()
+        self._fill.raise_()   # (the episode boundaries may have moved; nothing is drawn and the state is as it was)
 
     def set_task_sampling(self, enabled=True, seed=0, n_tasks=None):
         """Draw every env's task uniformly from the filled rows of the task table at each reset / auto-reset, on
@@ -337,17 +577,13 @@ class VecGridWorld:
         for k in self._STATE_KEYS:
             getattr(self, k).copy_(state[k])
         self._have_tasks = True
-        self._obs_moved()
-        self._mask_moved()
+        self._follow(draw=False)
 
     # ---- reset / step ----
     def _need_tasks(self):
         if not self._have_tasks:
             raise ValueError('Task is not initialized! Initialize task before working with the environment '
                              'using .set_tasks')
-
-    def obs(self):
-        return self._obs.copy()
 
     def dense(self):
         """Packed COPIES of the per-step results for consumers that cannot take strided views (see _make_views):
@@ -363,13 +599,8 @@ class VecGridWorld:
         L.check(self.lib.igw_reset(self.ctx, None if m is None else C.c_void_p(m.data_ptr()),
                                    L.RESET_KEEP_SIZE if keep_size else 0, self._stream()), 'igw_reset')
         self._mask_keep = m
-        obs = self.obs()
-        if self._pov is not None:
-            self._draw(restart=None if m is None else m.reshape(-1), fill=m is None)
-            self._pov.add_to(obs)
-        if self._mask is not None:
-            _mask_rows(self, self._mask, False, None, self._stream())
-        return obs
+        self._follow(None if m is None else m.reshape(-1), fill=m is None)
+        return self.obs()
 
     @staticmethod
     def _check_camera(cam):
@@ -396,106 +627,48 @@ class VecGridWorld:
         [N]; flying: float32 / int32) go straight to the C ABI: no conversion, no copy, one ctypes call."""
         if not self._have_tasks:
             self._need_tasks()
-        N = self.num_envs
-        if not (self.walk_dict or self.flying):
-            a = actions
-            if not (type(a) is torch.Tensor and a.dtype is torch.int32 and a.is_cuda and a.is_contiguous()):
-                a = torch.as_tensor(actions, device=self.device).to(torch.int32).contiguous()
-            if a.numel() != N:
-                raise ValueError(f'walking action needs {N} entries, got {a.numel()}')
-            rc = self.lib.igw_step_walking(self.ctx, a.data_ptr(), torch._C._cuda_getCurrentRawStream(self._dev_index))
-            if rc:
-                L.check(rc, 'igw_step_walking')
-            self._act_keep = a
-        else:
-            self._step_dict(actions, N)
-        obs = self._obs.copy()
-        if self._pov is not None:
-            self._draw(restart=self.done if self.autoreset else None)
-            self._pov.add_to(obs)
-        if self._mask is not None:
-            _mask_rows(self, self._mask, False, None, self._stream())
-        return obs, self.reward, self.done, {}
+        bufs = self._action_buffers(actions)
+        sp = self._space
+        rc = getattr(self.lib, sp.step)(self.ctx, *[b.data_ptr() for b in bufs],
+                                         torch._C._cuda_getCurrentRawStream(self._dev_index))
+        if rc:
+            L.check(rc, sp.step)
+        self._act_keep = bufs   # the launch reads them asynchronously
+        self._follow(self._ended())
+        return self._obs.copy(), self.reward, self.done, {}
 
-    def _step_dict(self, actions, N):
-        """The launch of step() for the two action spaces that take a dict: walking with discretize=False, flying."""
-        dev = self.device
-        self._check_camera(actions['camera'])
-
-        def dev_t(x, dt):   # already a contiguous device tensor of the kernel's dtype: as is
-            if type(x) is torch.Tensor and x.dtype is dt and x.is_cuda and x.is_contiguous():
-                return x
-            return torch.as_tensor(x, device=dev).to(dt).contiguous()
-        if self.walk_dict:
-            if 'buttons' in actions:
-                b = dev_t(actions['buttons'], torch.uint8).reshape(-1, 8)
-            else:  # the reference's Dict keys (env.py:60-70), one array per key
-                b = torch.stack([torch.as_tensor(np.asarray(actions[k]), device=dev).to(torch.uint8).reshape(-1)
-                                 for k in ('forward', 'back', 'left', 'right', 'jump', 'attack', 'use', 'hotbar')],
-                                dim=1).contiguous()
-            if b.shape[0] != N:
-                raise ValueError(f'walking Dict action needs {N} rows of 8 buttons, got {tuple(b.shape)}')
-            cam = dev_t(actions['camera'], torch.float32)
-            if cam.numel() != 2 * N:
-                raise ValueError(f'walking Dict action needs camera [{N},2], got {tuple(cam.shape)}')
-            L.check(self.lib.igw_step_walking_dict(self.ctx, b.data_ptr(), cam.data_ptr(), self._stream()),
-                    'igw_step_walking_dict')
-            self._act_keep = (b, cam)
-        else:
-            mv, cam = dev_t(actions['movement'], torch.float32), dev_t(actions['camera'], torch.float32)
-            inv, pl = dev_t(actions['inventory'], torch.int32), dev_t(actions['placement'], torch.int32)
-            if mv.numel() != 3 * N or cam.numel() != 2 * N or inv.numel() != N or pl.numel() != N:
-                raise ValueError(f'flying action needs movement [{N},3], camera [{N},2], inventory [{N}], placement [{N}]')
-            rc = self.lib.igw_step_flying(self.ctx, mv.data_ptr(), cam.data_ptr(), inv.data_ptr(), pl.data_ptr(),
-                                          torch._C._cuda_getCurrentRawStream(self._dev_index))
-            if rc:
-                L.check(rc, 'igw_step_flying')
-            self._act_keep = (mv, cam, inv, pl)
-
-    # ---- which actions would act (libigw_query.so, include/igw_query.h) ----
-    def action_mask(self, out=None, look=False, sample=None):
-        """Which of the 18 walking actions would act on every env's CURRENT state (after a step that ended an episode of
-        an auto-reset env: the new episode's): uint8 [N, 18], 1 where the action would do something -- the place / break
-        / hotbar actions would change the grid, a jump would start, the pitch would move; the no-op, the moves and the
-        yaw actions are always 1 (DESIGN.md section 10; names in query.ACTION_NAMES).  One igw_action_mask launch on the
-        current stream; with `out` (a contiguous uint8 device tensor of that shape) nothing is allocated, so the call
-        can be captured.  look=True also returns int16 [N, 2]: the grid cell (index into the flat [9 * 11 * 11] grid)
-        that action 16 would clear and the one action 17 would fill, -1 where they would do nothing.  sample=(seed, t)
-        also returns int32 [N]: one action per env drawn uniformly from the set bits of its mask, a counter RNG keyed by
-        (seed, global env index, t) (include/igw_query.h) -- a masked random policy without a host round trip.  The
-        result is the mask alone or the tuple (mask, look, actions) of what was asked for; with look / sample `out` may
-        be the tuple of tensors to write.  Discrete(18) walking only: ValueError for flying and Dict-action envs."""
-        return _mask_rows(self, out, look, sample, self._stream())
-
-    def _mask_moved(self):
-        """The state moved without a step (a fused rollout, load_state_dict): obs['action_mask'] follows it."""
-        if self._mask is not None:
-            _mask_rows(self, self._mask, False, None, self._stream())
+    def _action_buffers(self, actions, steps=None):
+        """The action buffers of the env's space (_SPACES) as the entries take them: contiguous device tensors of the
+        kernel's dtypes, for one step (steps=None; any shape of N rows) or as [T, N, ...] sequences (steps = who asks).
+        A tensor that already is one is passed on as it is; anything else is converted -- except for
+        steps='capture_steps', whose graph reads the caller's buffers at replay time: ValueError."""
+        sp, N, dev, bufs = self._space, self.num_envs, self.device, []
+        for (key, dt, shape), count in zip(sp.buffers, sp.counts):
+            if key is None:
+                x = actions
+            elif key == 'buttons' and steps is None and 'buttons' not in actions:   # the reference's keys, one array each
+                x = torch.stack([torch.as_tensor(np.asarray(actions[k]), device=dev).to(dt).reshape(-1)
+                                 for k in BUTTONS], dim=1)
+            else:
+                x = actions[key]
+            if not (type(x) is torch.Tensor and x.dtype is dt and x.is_cuda and x.is_contiguous()):
+                if steps == 'capture_steps':
+                    raise ValueError(f'capture_steps: {key or "actions"} must be a contiguous {dt} device tensor '
+                                     f'[T, {", ".join(map(str, (N, *shape)))}]')
+                if key == 'camera':   # (host data only: _check_camera does not read a device tensor back)
+                    self._check_camera(x)
+                x = torch.as_tensor(x, device=dev).to(dt).contiguous()
+            if steps is None:
+                ok = x.numel() == N * count
+            else:
+                ok = tuple(x.shape[1:]) == (N, *shape) and x.dim() == 2 + len(shape) and \
+                    (not bufs or x.shape[0] == bufs[0].shape[0])
+            if not ok:
+                raise sp.mismatch(steps or 'step', N, key, x, 'T' if steps else '')
+            bufs.append(x)
+        return bufs
 
     # ---- first-person frames (libigw_render.so, include/igw_render.h) ----
-    def _draw(self, stream=None, restart=None, fill=False, pending=True):
-        """What reset / step draw after their launch (renderer='hip'); on the current stream unless one is given.
-        `restart` / `fill` are the stack's restart rule of this draw (pov_obs; ignored without); pending=False (a
-        capture's draws) leaves the "next draw fills" flag alone."""
-        if pending and self._pov.obs is not None:
-            fill = _take_obs_fill(self) or fill
-        self._pov.draw(self, stream, None, restart, fill)
-
-    def _obs_moved(self):
-        """The state moved without a draw: the next draw restarts every env's stack (pov_obs)."""
-        self._obs_fill = True
-        for e in [self] + self._children:
-            e._obs_fill = True
-        if self._obs_flags is not None:
-            self._obs_flags[0].fill_(1)
-
-    def _obs_device_flags(self):
-        """uint8 [2, N] on the device: row 0 the "next draw fills" flag per env, row 1 a scratch restart mask."""
-        if self._obs_flags is None:
-            self._obs_flags = torch.zeros((2, self.num_envs), dtype=torch.uint8, device=self.device)
-            self._obs_flags[0].fill_(int(self._obs_fill))
-        return self._obs_flags
-
     def render_pov_obs(self, spec, out=None, restart=None, fill=False, frame=None):
         """The observation of every env's CURRENT state in the layout `spec` (a render.ObsSpec or a dict), for callers
         who keep their own stack: one igw_render_pov_obs launch on the current stream that shifts this frame into `out`
@@ -513,26 +686,6 @@ class VecGridWorld:
         of 8 up to 256 -- e.g. render.load_atlas('texture.png') of the reference for its look.  Default: the flat-colour
         atlas of render.default_atlas()."""
         self._render_atlas = R.device_atlas(atlas, self.device)
-
-    def _atlas(self):
-        if self._render_atlas is None:
-            self.set_render_atlas(None)
-        return self._render_atlas
-
-    def render_pov(self, out=None, channels=3, size=None, outputs=None, codec=None, quality=90):
-        """The first-person frame of every env's CURRENT state (see _make_views for auto-reset envs): uint8
-        [N, H, W, channels] with W, H = size (default render_size), row 0 the top image row, channels 3 (RGB) or 4 (RGBA,
-        what the reference's Renderer.render() returns).  One launch on the current stream; with `out` (a contiguous
-        uint8 device tensor of that shape) nothing is allocated, so the call can be captured in a graph.
-        outputs (a tuple of 'rgb', 'depth', 'label', 'surface') returns a dict name -> tensor instead, from one
-        igw_render_pov_aux launch: the frame and / or the [N, H, W] planes float32 depth, uint8 label, int16 surface
-        (include/igw_render.h); `out` is then a dict of preallocated tensors under those names, or None.
-        codec='jpeg' returns (buf, sizes) of codec.encode_jpeg instead: the frames are drawn, then encoded at `quality`
-        by a second launch on the same stream; `out` is then the (buf, sizes) pair to encode into, or None."""
-        def draw(out=None, outputs=None):
-            return _render_rows(self, out, channels, size, outputs, self._stream())
-        res = K.encoded(codec, outputs, quality, out, draw)
-        return draw(out, outputs) if res is None else res
 
     def render_views(self, poses, rows=None, what='grid', **kw):
         """Views of the batch from cameras of the caller's choice (visualizer.render_views): uint8 [M, H, W, channels]
@@ -577,22 +730,26 @@ class VecGridWorld:
         self._need_tasks()
         return StepGraph(self, actions, record, chains)
 
-    def step_walking_ptr(self, actions_i32):
-        """Hot-loop variant: `actions_i32` is already a contiguous int32 device tensor [N].  It launches the step and,
-        with action_mask=True, the mask (obs['action_mask'] follows the state); it does NOT draw: obs['pov'] and the
-        other render outputs keep what the last step() / reset() left."""
-        if actions_i32.numel() != self.num_envs:
-            raise ValueError(f'walking action needs {self.num_envs} entries, got {actions_i32.numel()}')
-        L.check(self.lib.igw_step_walking(self.ctx, actions_i32.data_ptr(), self._stream()), 'igw_step_walking')
-        self._mask_moved()
+    def _before_capture(self):
+        """What _follow_captured reads and a capture may not allocate."""
+        if self._pov is not None:
+            self._atlas()
+            if self._pov.stacked:
+                self._fill.on_device(self)
+
+    def _replayed(self, chains):
+        """What StepGraph.replay returns, step()'s result; the first draws of the graph's `chains` (its sub-batches, if
+        it has any) took the stacks' fill flags."""
+        if self.pov_obs is not None:
+            self._fill.lowered(self, *chains)
+        return self._obs.copy(), self.reward, self.done, {}
 
     def rollout(self, T, seed, t0=0, env_offset=0):
         """T fused walking steps per env with counter-RNG actions and auto-reset (one launch)."""
         self._need_tasks()
         L.check(self.lib.igw_rollout_walking(self.ctx, int(T), int(seed), int(t0), int(env_offset),
                                              self._stream()), 'igw_rollout_walking')
-        self._obs_moved()
-        self._mask_moved()
+        self._follow(draw=False)
 
     def rollout_actions(self, actions, return_rewards=False):
         """Fused replay of a recorded action sequence: `actions` int32 [T, N] (Discrete(18) ids), or for the flying action
@@ -600,42 +757,22 @@ class VecGridWorld:
         T calls of step(), in one launch without a barrier between the steps of different envs (the context's
         autoreset setting applies).  With return_rewards: (rewards float32 [T, N], dones uint8 [T, N])."""
         self._need_tasks()
-        N, dev = self.num_envs, self.device
-        if self.walk_dict:
+        N, dev, sp = self.num_envs, self.device, self._space
+        if sp.rollout is None:
             raise L.IgwError('rollout_actions: Discrete(18) walking and flying only')
         if self._traj is not None:
             raise L.IgwError('rollout / rollout_actions do not write the episode log: disable_trajectory_log() first')
-        if self.flying:   # dict(movement f32[T,N,3], camera f32[T,N,2], inventory i32[T,N], placement i32[T,N])
-            self._check_camera(actions['camera'])
-            mv = torch.as_tensor(actions['movement'], device=dev).to(torch.float32).contiguous()
-            cam = torch.as_tensor(actions['camera'], device=dev).to(torch.float32).contiguous()
-            inv = torch.as_tensor(actions['inventory'], device=dev).to(torch.int32).contiguous()
-            plc = torch.as_tensor(actions['placement'], device=dev).to(torch.int32).contiguous()
-            T = mv.shape[0]
-            if tuple(mv.shape) != (T, N, 3) or tuple(cam.shape) != (T, N, 2) or tuple(inv.shape) != (T, N) or tuple(plc.shape) != (T, N):
-                raise ValueError(f'flying actions must be [T,{N},3], [T,{N},2], [T,{N}], [T,{N}]')
-            keep = (mv, cam, inv, plc)
-        else:
-            a = torch.as_tensor(actions, device=dev)
-            if a.dim() != 2 or a.shape[1] != N:
-                raise ValueError(f'actions must be [T, {N}], got {tuple(a.shape)}')
-            a = a.to(torch.int32).contiguous()
-            T = a.shape[0]
-            keep = (a,)
+        bufs = self._action_buffers(actions, 'rollout_actions')
+        T = int(bufs[0].shape[0])
         rw = dn = None
         if return_rewards:
             rw = torch.empty((T, N), dtype=torch.float32, device=dev)
             dn = torch.empty((T, N), dtype=torch.uint8, device=dev)
         rp, dp = (rw.data_ptr() if rw is not None else None), (dn.data_ptr() if dn is not None else None)
-        if self.flying:
-            L.check(self.lib.igw_rollout_flying_actions(self.ctx, mv.data_ptr(), cam.data_ptr(), inv.data_ptr(), plc.data_ptr(),
-                                                        int(T), rp, dp, self._stream()), 'igw_rollout_flying_actions')
-        else:
-            L.check(self.lib.igw_rollout_walking_actions(self.ctx, a.data_ptr(), int(T), rp, dp, self._stream()),
-                    'igw_rollout_walking_actions')
-        self._keep = keep  # the launch reads them asynchronously
-        self._obs_moved()
-        self._mask_moved()
+        L.check(getattr(self.lib, sp.rollout)(self.ctx, *[b.data_ptr() for b in bufs], T, rp, dp, self._stream()),
+                sp.rollout)
+        self._keep = bufs  # the launch reads them asynchronously
+        self._follow(draw=False)
         return (rw, dn) if return_rewards else None
 
     def fill_actions(self, n_steps, seed, t0=0, env_offset=0):
@@ -682,10 +819,7 @@ class VecGridWorld:
     def stats(self):
         """Device counters of this env and of its sub-batches (VecGridWorld.split).  `steps`: env-steps executed, counted
         on the device by every step launch and fused rollout (`rollout_steps` is the same counter's old name)."""
-        s = self.stats_buf.sum(0)
-        for c in self._children:
-            s = s + c.stats_buf.sum(0)
-        s = s.cpu()
+        s = self.stats_tensor().cpu()
         return {'changed': int(s[L.STAT_CHANGED]), 'resets': int(s[L.STAT_RESETS]),
                 'steps': int(s[L.STAT_STEPS]), 'rollout_steps': int(s[L.STAT_STEPS]), 'rescans': int(s[L.STAT_RESCANS]),
                 'bad_poses': int(s[L.STAT_BAD_POSE]), 'bad_actions': int(s[L.STAT_BAD_ACTION]),
@@ -734,29 +868,14 @@ class StepGraph:
         # alive, so a stale graph can neither run a stale configuration silently nor write into freed memory.
         self.config_epoch = env.config_epoch
         self._held = env._traj
-
-        def need(x, dt, shape, what):
-            if not (type(x) is torch.Tensor and x.is_cuda and x.dtype is dt and x.is_contiguous() and tuple(x.shape[1:]) == shape):
-                raise ValueError(f'capture_steps: {what} must be a contiguous {dt} device tensor [T, {", ".join(map(str, shape))}]')
-            return x
-        if env.flying:
-            self.buffers = (need(actions['movement'], torch.float32, (N, 3), 'movement'), need(actions['camera'], torch.float32, (N, 2), 'camera'),
-                            need(actions['inventory'], torch.int32, (N,), 'inventory'), need(actions['placement'], torch.int32, (N,), 'placement'))
-            fn, row_bytes = env.lib.igw_step_flying, (12, 8, 4, 4)
-        elif env.walk_dict:
-            self.buffers = (need(actions['buttons'], torch.uint8, (N, 8), 'buttons'), need(actions['camera'], torch.float32, (N, 2), 'camera'))
-            fn, row_bytes = env.lib.igw_step_walking_dict, (8, 8)
-        else:
-            self.buffers = (need(actions, torch.int32, (N,), 'actions'),)
-            fn, row_bytes = env.lib.igw_step_walking, (4,)
+        self.buffers = tuple(env._action_buffers(actions, 'capture_steps'))   # (validated; never converted)
         self.T = T = int(self.buffers[0].shape[0])
-        if T < 1 or any(b.shape[0] != T for b in self.buffers):
+        if T < 1:
             raise ValueError('capture_steps: every action buffer needs the same number of steps T >= 1')
         self.outs = torch.zeros((T, N, L.OUT_BYTES), dtype=torch.uint8, device=dev) if record else None
-        ptrs = [tuple(b[t].data_ptr() for b in self.buffers) for t in range(T)]
+        fn, row_bytes = getattr(env.lib, env._space.step), env._space.row_bytes
         self.graph = torch.cuda.CUDAGraph()
-        cap = torch.cuda.Stream(device=dev)
-        cap.wait_stream(torch.cuda.current_stream(dev))
+        cur = torch.cuda.current_stream(dev)
         # (thread-local: other threads of the process -- an RCCL watchdog, a data loader -- may touch the runtime)
         # chains > 1: one context, one stream and ONE LINEAR GRAPH per chain, replayed side by side on their streams.
         # (Measured, profiles/r05_chains.txt: captured as parallel BRANCHES of one graph the chains do not overlap --
@@ -764,44 +883,20 @@ class StepGraph:
         # step against 10.9 for the single chain -- while kernels of different STREAMS do run concurrently.)
         self.subs = env.split(chains) if chains > 1 else None   # (kept alive with the graphs)
         self.graphs = [self.graph] + [torch.cuda.CUDAGraph() for _ in range(chains - 1)]
-        if env._pov is not None:
-            env._atlas()   # (allocated before the capture)
-        # a stack of K > 1 frames takes every step's frame: the draw follows each step launch of its chain.  The first
-        # draw of a replay restarts the envs whose "next draw fills" byte is set (device memory, so it holds at replay
-        # time) beside those the eager rule restarts, and clears the bytes.
-        stacked = env._pov is not None and env._pov.obs is not None and env._pov.spec.stack > 1
-        flags = env._obs_device_flags() if stacked else None
-        self.streams = [cap] + [torch.cuda.Stream(device=dev) for _ in range(chains - 1)]
-        for k in range(chains):
-            st = self.streams[k]
-            st.wait_stream(torch.cuda.current_stream(dev))
-            ctx = env.ctx if chains == 1 else self.subs[k].ctx
-            lo, n = (0, N) if chains == 1 else (self.subs[k].lo, self.subs[k].num_envs)
-            offs = tuple(b * lo for b in row_bytes)
-            with torch.cuda.graph(self.graphs[k], stream=st, capture_error_mode='thread_local'):
+        self.streams = [torch.cuda.Stream(device=dev) for _ in range(chains)]
+        env._before_capture()
+        for part, graph, st in zip(self.subs or [env], self.graphs, self.streams):
+            st.wait_stream(cur)
+            lo, n = part.lo, part.num_envs
+            ptrs = [[b[t].data_ptr() + lo * rb for b, rb in zip(self.buffers, row_bytes)] for t in range(T)]
+            with torch.cuda.graph(graph, stream=st, capture_error_mode='thread_local'):
                 h = C.c_void_p(st.cuda_stream)
                 for t in range(T):
-                    L.check(fn(ctx, *(p + o for p, o in zip(ptrs[t], offs)), h), 'step (capture)')
+                    L.check(fn(part.ctx, *ptrs[t], h), 'step (capture)')
                     if record:
                         self.outs[t, lo:lo + n].copy_(env.out_buf[lo:lo + n])
-                    if stacked:
-                        e = env if chains == 1 else self.subs[k]
-                        done = env.done[lo:lo + n] if env.autoreset else None
-                        if t == 0:
-                            first, mask = flags[0, lo:lo + n], flags[1, lo:lo + n]
-                            if done is None:
-                                mask.copy_(first)
-                            else:
-                                torch.bitwise_or(done, first, out=mask)
-                            first.zero_()
-                            done = mask
-                        e._draw(h, restart=done, pending=False)
-                    if env._mask is not None:   # obs['action_mask'] follows every step of its chain
-                        e = env if chains == 1 else self.subs[k]
-                        _mask_rows(e, e._mask, False, None, h)
-                if env._pov is not None and not stacked:   # the frame (and planes) of the state after the last step
-                    (env if chains == 1 else self.subs[k])._draw(h, pending=False)
-            torch.cuda.current_stream(dev).wait_stream(st)
+                    part._follow_captured(h, t == 0, t == T - 1)
+            cur.wait_stream(st)
         if record:
             f = self.outs.view(torch.float32)
             self.rewards, self.dones = f[:, :, 12], self.outs[:, :, 52]
@@ -832,50 +927,32 @@ class StepGraph:
                     g.replay()
             for st in self.streams:
                 cur.wait_stream(st)
-        if env._pov is not None and env._pov.obs is not None:   # the graph's first draw took the flag (a stack of one
-            env._obs_fill = False                                # frame has nothing to restart)
-            for c in self.subs or ():
-                c._obs_fill = False
-        obs = env._obs.copy()
-        return (obs if env._pov is None else env._pov.add_to(obs)), env.reward, env.done, {}
+        return env._replayed(self.subs or ())
 
 
-class SubBatch:
+class SubBatch(_Rows):
     """Rows [lo, lo + n) of a VecGridWorld behind their own igw context and stream (VecGridWorld.split).
     The context carries the parent's global env offset, so device-side task generators draw the streams the
     whole batch would draw, and inherits the parent's generator settings."""
+    _SHARED = ('lib', 'device', 'render_size', 'pov_outputs', 'autoreset', 'flying', 'walk_dict', 'select_and_place')
+    _VIEWS = ('agent_pos', 'inventory', 'compass', 'reward', 'done', 'grid')   # VecGridWorld._make_views
 
     def __init__(self, parent, lo, n, stream):
-        self.parent, self.lo, self.num_envs, self.stream = parent, lo, n, stream
-        self.lib, self.device = parent.lib, parent.device
+        self.parent, self.lo, self.stream = parent, lo, stream
+        for k in self._SHARED:
+            setattr(self, k, getattr(parent, k))
         cfg = L.Config.from_buffer_copy(parent.cfg)
         cfg.num_envs = n
         cfg.env_index_base = parent.env_index_base + lo
         if cfg.lanes_per_env == 0:   # the group width the library chose for the WHOLE batch (include/igw.h: IGW_AUTO_*)
             cfg.lanes_per_env = L.auto_lanes(parent.num_envs)
-        self.cfg = cfg
-        self.ctx = C.c_void_p()
-        L.check(self.lib.igw_create(C.byref(cfg), C.byref(self.ctx)), 'igw_create')
-        sl = slice(lo, lo + n)
-        self.stats_buf = torch.zeros_like(parent.stats_buf)
-        rows = lambda t: t[sl].data_ptr()  # noqa: E731
-        ptrs = [rows(parent.grid_buf), rows(parent.occ_buf), rows(parent.hist_buf), rows(parent.agent_buf), rows(parent.aux_buf),
-                parent.task_target.data_ptr(), parent.task_start.data_ptr(), parent.task_start_occ.data_ptr(),
-                parent.task_meta.data_ptr(), parent.task_index.data_ptr(), rows(parent.out_buf), self.stats_buf.data_ptr()]
-        L.check(self.lib.igw_bind_buffers(self.ctx, C.byref(L.Buffers(*ptrs))), 'igw_bind_buffers')
-        self.agent_pos, self.inventory = parent.agent_pos[sl], parent.inventory[sl]
-        self.compass, self.reward, self.done = parent.compass[sl], parent.reward[sl], parent.done[sl]
-        self.grid = parent.grid[sl]
-        self.render_size = parent.render_size
-        self.pov_outputs = parent.pov_outputs
-        self._pov = None if parent._pov is None else parent._pov.rows(sl)
-        self._rows = tuple(t[sl] for t in parent._rows)
-        self.pov = self._pov.tensors.get('rgb') if self._pov else None
-        self.pov_obs = self._pov.obs if self._pov else None
-        self.autoreset, self._obs_fill, self._obs_flags = parent.autoreset, parent._obs_fill, None
-        self.flying, self.walk_dict, self.select_and_place = parent.flying, parent.walk_dict, parent.select_and_place
-        self.env_index_base = cfg.env_index_base
-        self._mask = None if parent._mask is None else parent._mask[sl]
+        self._open(cfg, torch.zeros_like(parent.stats_buf))
+        sl = self._sl
+        for k in self._VIEWS:
+            setattr(self, k, getattr(parent, k)[sl])
+        self._follow_with(parent._pov and parent._pov.rows(sl), None if parent._mask is None else parent._mask[sl])
+        if parent in parent._fill.drawn:   # (a sub-batch of a batch whose stacks are current starts with them)
+            parent._fill.lowered(self)
         self._inherit_sampling()
 
     def _inherit_sampling(self):
@@ -888,76 +965,9 @@ class SubBatch:
         else:  # generated rows are indexed by the context's local env, a sub-batch would overwrite rows of another
             raise L.IgwError('the RandomTasks generator cannot be combined with sub-batches')
 
-    def __del__(self):
-        if getattr(self, 'ctx', None):
-            self.lib.igw_destroy(self.ctx)
-            self.ctx = None
-
-    def obs(self):
-        o = _state_obs(self)
-        if self._mask is not None:
-            o['action_mask'] = self._mask
-        return o if self._pov is None else self._pov.add_to(o)
-
-    def action_mask(self, out=None, look=False, sample=None):
-        """VecGridWorld.action_mask for this sub-batch's rows, on its own stream."""
-        for t in out if isinstance(out, (tuple, list)) else (out,):
-            if torch.is_tensor(t):
-                t.record_stream(self.stream)
-        res = _mask_rows(self, out, look, sample, self._stream(), self.stream)
-        for t in res if isinstance(res, tuple) else (res,):
-            t.record_stream(self.stream)
-        return res
-
-    def _mask_moved(self):
-        if self._mask is not None:
-            _mask_rows(self, self._mask, False, None, self._stream())
-
-    def _stream(self):
-        return C.c_void_p(self.stream.cuda_stream)
-
-    def _draw(self, stream=None, restart=None, fill=False, pending=True):
-        """What reset / step draw after their launch (renderer='hip'), on this sub-batch's stream unless one is given
-        (a capture's); `restart`, `fill` and `pending` as for VecGridWorld._draw."""
-        if self._pov is not None:
-            if pending and self._pov.obs is not None:
-                fill = _take_obs_fill(self) or fill
-            self._pov.draw(self, stream, self.stream, restart, fill)
-
-    def _atlas(self):
-        return self.parent._atlas()
-
-    def render_pov(self, out=None, channels=3, size=None, outputs=None, codec=None, quality=90):
-        """VecGridWorld.render_pov for this sub-batch's rows, on its own stream."""
-        given = out.values() if isinstance(out, dict) else out if isinstance(out, (tuple, list)) else (out,)
-        for t in given:
-            if torch.is_tensor(t):
-                t.record_stream(self.stream)
-
-        def draw(out=None, outputs=None):
-            return _render_rows(self, out, channels, size, outputs, self._stream(), self.stream)
-        with torch.cuda.stream(self.stream):
-            res = K.encoded(codec, outputs, quality, out, draw)
-        if res is None:
-            return draw(out, outputs)
-        for t in res:
-            t.record_stream(self.stream)
-        return res
-
-    def step_walking_ptr(self, actions_i32):
-        """actions_i32: contiguous int32 device tensor [n]; launched on this sub-batch's stream (the tensor is
-        marked as in use there, so the caching allocator does not recycle it while the kernel reads it)."""
-        if actions_i32.numel() != self.num_envs:
-            raise ValueError(f'walking action needs {self.num_envs} entries, got {actions_i32.numel()}')
-        actions_i32.record_stream(self.stream)
-        L.check(self.lib.igw_step_walking(self.ctx, actions_i32.data_ptr(), self._stream()), 'igw_step_walking')
-        self._draw(restart=self.done if self.autoreset else None)
-        self._mask_moved()
-
     def reset(self):
         L.check(self.lib.igw_reset(self.ctx, None, 0, self._stream()), 'igw_reset')
-        self._draw(fill=True)
-        self._mask_moved()
+        self._follow(fill=True)
         return self.obs()
 
     def synchronize(self):
@@ -968,39 +978,21 @@ class SubBatch:
         torch.cuda.current_stream(self.device).wait_stream(self.stream)
 
 
-def _state_obs(e):
-    """The four state keys of an observation: views of the records of a VecGridWorld or of a SubBatch's rows."""
-    return {'agentPos': e.agent_pos, 'inventory': e.inventory, 'compass': e.compass.unsqueeze(1), 'grid': e.grid}
-
-
 class _Pov:
     """The persistent outputs of renderer='hip': output name -> tensor as pov_outputs names them, for the whole batch
-    or, through rows(), for a SubBatch's slice of the same memory.  The default, ('rgb',), is drawn by the plain entry
-    (render.launch with outputs=None); anything else by one _aux launch.  With pov_obs, `obs` is the stack tensor
-    [N, K * planes, H, W] of `spec` and `tensors` holds the frame or nothing (pov_frame=False): one
-    igw_render_pov_obs launch (render.launch_obs) draws both."""
+    or, through rows(), for a SubBatch's slice of the same memory (_Rows._draw draws them).  The default, ('rgb',), is
+    drawn by the plain entry (render.launch with outputs=None); anything else by one _aux launch.  With pov_obs, `obs`
+    is the stack tensor [N, K * planes, H, W] of `spec` and `tensors` holds the frame or nothing (pov_frame=False): one
+    igw_render_pov_obs launch (render.launch_obs) draws both; `stacked` says that the stack holds more than the
+    current frame, so that every frame has to enter it."""
 
     def __init__(self, tensors, spec=None, obs=None):
         self.tensors, self.spec, self.obs = tensors, spec, obs
         self.plain = tuple(tensors) == ('rgb',) and obs is None
+        self.stacked = obs is not None and spec.stack > 1
 
     def rows(self, sl):
         return _Pov({k: t[sl] for k, t in self.tensors.items()}, self.spec, None if self.obs is None else self.obs[sl])
-
-    def draw(self, env, stream=None, own=None, restart=None, fill=False):
-        """Draws the tensors from env's state rows on `stream`; without one on the env's own, where the tensors are
-        then marked as in use if that is a side stream, `own` (a SubBatch's).  `restart` (None or a uint8 tensor [n]
-        at any stride) and `fill` are the stack's restart rule of this draw (igw_render_obs); ignored without pov_obs."""
-        if stream is None:
-            stream = env._stream()
-            for t in (*self.tensors.values(), *(() if self.obs is None else (self.obs,))) if own is not None else ():
-                t.record_stream(own)
-        if self.obs is not None:
-            _render_obs_rows(env, self.spec, self.obs, self.tensors.get('rgb'), restart, fill, stream)
-        elif self.plain:
-            _render_rows(env, self.tensors['rgb'], 3, None, None, stream)
-        else:
-            _render_rows(env, self.tensors, 3, None, tuple(self.tensors), stream)
 
     def add_to(self, obs):
         """Adds the tensors to an observation dict, 'rgb' as 'pov', the planes under their names and the stack as
@@ -1010,15 +1002,6 @@ class _Pov:
         if self.obs is not None:
             obs['pov_obs'] = self.obs
         return obs
-
-
-def _take_obs_fill(env):
-    """Whether the draw that is about to be launched for `env` (a VecGridWorld or a SubBatch) restarts every stack
-    because the state moved without a draw; clears the flag, on the device too where a graph reads it."""
-    fill, env._obs_fill = env._obs_fill, False
-    if fill and env._obs_flags is not None:
-        env._obs_flags[0].zero_()
-    return fill
 
 
 def _render_rows(env, out, channels, size, outputs, stream, alloc_stream=None):
@@ -1057,9 +1040,7 @@ def task_eval(targets, grids, full_grids=None, invariant=None, device='cuda:0'):
     dev = torch.device(device)
     t, g, f = _as_rows(targets, dev), _as_rows(grids, dev), _as_rows(full_grids, dev)
     n = t.shape[0]
-    inv = None
-    if invariant is not None:
-        inv = torch.as_tensor(np.broadcast_to(np.asarray(invariant, dtype=np.uint8), (n,)).copy(), device=dev)
+    inv = _invariant(invariant, n, dev)
     mi = torch.zeros(n, dtype=torch.int32, device=dev)
     am = torch.zeros((n, 3), dtype=torch.int32, device=dev)
     ts = torch.zeros(n, dtype=torch.int32, device=dev)
