@@ -17,3 +17,5 @@ from . import codec  # noqa: F401,E402
 from .codec import encode_jpeg, jpeg_bytes  # noqa: F401,E402
 from . import query  # noqa: F401,E402
 from .query import ACTION_NAMES as action_mask_names  # noqa: F401,E402
+from . import goal  # noqa: F401,E402
+from .goal import goal_world  # noqa: F401,E402

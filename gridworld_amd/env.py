@@ -372,6 +372,18 @@ class GridWorld:
         (VecGridWorld.action_mask).  ValueError for the flying and Dict action spaces."""
         return self._vec.action_mask()[0].cpu().numpy().astype(np.bool_)
 
+    def goal(self):
+        """Where the reward wants the target on the state of the last reset / step (VecGridWorld.goal, DESIGN.md
+        section 11), as numpy: align int8 [3], fit int16 [4], want / todo int8 [9, 11, 11] and -- in the Discrete(18)
+        action space -- gain float32 [18], ends bool [18]: the reward and `done` of this env's own step(a), before any
+        wrapper."""
+        v = self._vec
+        res = v.goal(want=True, todo=True, gain=not (v.flying or v.walk_dict))
+        out = {k: t[0].cpu().numpy() for k, t in res.items()}
+        if 'ends' in out:
+            out['ends'] = out['ends'].astype(np.bool_)
+        return out
+
     def render(self):
         """Renderer.render() (gridworld/render.py:129-144): the current frame as RGBA uint8 [H, W, 4], row 0 on top."""
         if not self._renders():

@@ -13,6 +13,7 @@ import torch
 
 from . import _lib as L
 from . import codec as K
+from . import goal as G
 from . import query as Q
 from . import render as R
 
@@ -145,10 +146,11 @@ class _Rows:
         self._sl = sl
         self._rows = (root.agent_buf[sl], root.grid_buf[sl], root.occ_buf[sl])   # the state a frame is drawn from
 
-    def _follow_with(self, pov, mask):
-        """The persistent tensors that follow the state (a _Pov or None; obs['action_mask'] or None): this range's
-        rows of them, and the observation dict that holds them beside the state's views."""
-        self._pov, self._mask = pov, mask
+    def _follow_with(self, pov, mask, goal=None):
+        """The persistent tensors that follow the state (a _Pov or None; obs['action_mask'] or None; the dict of the
+        goal query's outputs or None): this range's rows of them, and the observation dict that holds them beside the
+        state's views."""
+        self._pov, self._mask, self._goal = pov, mask, goal
         self.pov = pov.tensors.get('rgb') if pov else None
         self.pov_obs = pov.obs if pov else None
         self._obs = {'agentPos': self.agent_pos, 'inventory': self.inventory, 'compass': self.compass.unsqueeze(1),
@@ -157,6 +159,10 @@ class _Rows:
             pov.add_to(self._obs)
         if mask is not None:
             self._obs['action_mask'] = mask
+        if goal is not None:
+            self._obs.update(goal)
+            if 'gain' in goal:
+                self._goal_scratch()   # (before the first launch that follows, which may be a captured one)
 
     def __del__(self):
         ctx = getattr(self, 'ctx', None)
@@ -189,7 +195,8 @@ class _Rows:
     # ---- what follows a launch ----
     def _follow(self, restart=None, fill=False, draw=True):
         """The ONE path after a launch that moved this range's state: the draw (renderer='hip'), then the action mask
-        (action_mask=True), on the range's stream.  `restart` / `fill` are the stack's restart rule of the draw
+        (action_mask=True), then the goal query (goal=...), on the range's stream.
+        `restart` / `fill` are the stack's restart rule of the draw
         (pov_obs; ignored without): a uint8 tensor [n] of the rows to restart -- a step's _ended(), reset(mask)'s
         mask -- or fill=True for every row (a full reset); the range's first draw after an undrawn move fills too.
         draw=False is the move that draws nothing (the fused rollouts, load_state_dict): it raises that flag."""
@@ -200,6 +207,7 @@ class _Rows:
                 fill = self._root()._fill.take(self) or fill
             self._draw(None, restart, fill)
         self._follow_mask()
+        self._follow_goal()
 
     def _follow_captured(self, stream, first, last):
         """_follow() after a step inside a captured chain, on the capture's stream (`first` / `last`: of the chain's
@@ -211,12 +219,32 @@ class _Rows:
             restart = self._ended()
             self._draw(stream, self._root()._fill.captured(self._sl, restart) if first else restart)
         self._follow_mask(stream)
+        self._follow_goal(stream)
         if last and pov is not None and not pov.stacked:
             self._draw(stream)
 
     def _follow_mask(self, stream=None):
         if self._mask is not None:
             _mask_rows(self, self._mask, False, None, self._stream() if stream is None else stream)
+
+    def _follow_goal(self, stream=None):
+        if self._goal is not None:
+            _goal_rows(self, tuple(self._goal), self._goal, self._stream() if stream is None else stream,
+                       captured=stream is not None)
+
+    def _goal_scratch(self):
+        """What gain=True needs beside its outputs, allocated once per range (on its stream) and kept, so that later
+        calls allocate nothing: the mask and look tensors of igw_action_mask, a copy of the agent records and a mask
+        nobody reads (_goal_rows)."""
+        tmp = getattr(self, '_goal_tmp', None)
+        if tmp is None:
+            n, dev = self.num_envs, self.device
+            with torch.cuda.stream(self.stream):
+                tmp = self._goal_tmp = (torch.zeros((n, Q.ACTIONS), dtype=torch.uint8, device=dev),
+                                        torch.zeros((n, 2), dtype=torch.int16, device=dev),
+                                        torch.zeros((n, L.AGENT_BYTES), dtype=torch.uint8, device=dev),
+                                        torch.zeros((n, Q.ACTIONS), dtype=torch.uint8, device=dev))
+        return tmp
 
     def _ended(self):
         """The stacks a step's draw restarts: those of the envs whose episode just ended if they auto-reset (the frame
@@ -252,6 +280,7 @@ class _Rows:
         # boundaries, it leaves the stacks' fill flag alone): its callers draw when they want a frame.
         if self.parent is None:
             self._follow_mask()
+            self._follow_goal()
         else:
             self._follow(self._ended())
 
@@ -272,6 +301,29 @@ class _Rows:
         self._in_use(*(out if isinstance(out, (tuple, list)) else (out,)))
         res = _mask_rows(self, out, look, sample, self._stream(), self.stream)
         self._in_use(*(res if isinstance(res, tuple) else (res,)))
+        return res
+
+    # ---- where the reward wants the target (libigw_goal.so, include/igw_goal.h) ----
+    def goal(self, want=False, todo=True, gain=False, out=None):
+        """Where the reward currently wants the target, what is left of it and -- gain=True -- what every action would
+        earn, for every env's CURRENT state: a dict of
+          align int8 [N, 3]    (dx, dz, rot) = Task.argmax_intersection of the live synthetic grid
+          fit   int16 [N, 4]   (max_int, target_size, size, cached_max_int)
+          want  int8 [N, 9, 11, 11] (want=True)   the synthetic target under that alignment, in the grid's frame
+          todo  int8 [N, 9, 11, 11] (todo=True)   want where the synthetic grid differs from it, else 0
+          gain  float32 [N, 18], ends uint8 [N, 18] (gain=True)   the reward and `done` that step(a) would return
+        want / todo are strided views of 1104-byte rows, as `grid` is.  One igw_goal launch on the range's stream;
+        gain=True first launches igw_action_mask there (twice: the mask of the state, and the cells of a copy of the
+        agent records with a full inventory, so that a colour that can be placed where the active one cannot has its
+        cell), into scratch tensors the range keeps.  `out`: a dict of tensors to write, as an earlier call returned
+        them; with every output given nothing is allocated (gain=True: from the range's second such call on), so the
+        call can be captured.  align / fit / want / todo work in every action space; gain=True raises ValueError
+        outside Discrete(18) walking and with size_reward=True (the wrapper's reward is not what is predicted)."""
+        names = ('align', 'fit') + (('want',) if want else ()) + (('todo',) if todo else ()) + \
+            (('gain', 'ends') if gain else ())
+        self._in_use(*(out or {}).values())
+        res = _goal_rows(self, names, out, self._stream(), self.stream)
+        self._in_use(*res.values())
         return res
 
     # ---- first-person frames (libigw_render.so, include/igw_render.h) ----
@@ -305,7 +357,7 @@ class VecGridWorld(_Rows):
                  size_reward=True, max_steps=250, right_placement_scale=1., wrong_placement_scale=0.1,
                  discretize=True, autoreset=False, num_tasks=None, lanes_per_env=0, debug_flags=0, env_index_base=0,
                  host_records=False, render=False, render_size=(64, 64), target_in_obs=False, vector_state=True, name='', fake=False,
-                 renderer=None, pov_outputs=('rgb',), pov_obs=None, pov_frame=True, action_mask=False):
+                 renderer=None, pov_outputs=('rgb',), pov_obs=None, pov_frame=True, action_mask=False, goal=False):
         """create_env's keyword arguments (gridworld/env.py:333-338) plus the batch's own: num_envs, device,
         autoreset (reset inside step), num_tasks (rows of the task table, default num_envs), lanes_per_env
         (0 = automatic), env_index_base (global index of env 0: rank / sub-batch offset), debug_flags (IGW_DIAG
@@ -332,7 +384,10 @@ class VecGridWorld(_Rows):
         store.  pov_obs goes with pov_outputs=('rgb',) only.
         action_mask=True (Discrete(18) walking only) adds obs['action_mask'], a persistent uint8 [N, 18] tensor: which
         actions would act on the state the observation shows (action_mask()), written by one
-        igw_action_mask launch on the same stream after the step / reset launch (and after the draw)."""
+        igw_action_mask launch on the same stream after the step / reset launch (and after the draw).
+        goal=True, or a tuple of 'want', 'todo', 'gain' (True = ('todo',)), adds obs['align'], obs['fit'] and the
+        outputs named (gain: obs['gain'] and obs['ends']): persistent tensors of goal()'s layout, rewritten by one
+        igw_goal launch after the mask's.  'gain' has goal(gain=True)'s conditions."""
         if renderer not in (None, 'hip'):
             raise ValueError(f"unknown renderer {renderer!r}; the one renderer is 'hip'")
         pov_outputs = R.check_outputs(pov_outputs)
@@ -420,8 +475,19 @@ class VecGridWorld(_Rows):
         self._fill = _FillFlag(N, dev)   # raised: the first draw fills
         if action_mask:
             Q.load()   # (built before the first step, not inside it)
+        goal = ('todo',) if goal is True else tuple(goal or ())
+        if [k for k in goal if k not in ('want', 'todo', 'gain')]:
+            raise ValueError(f"goal names 'want', 'todo' and / or 'gain', got {goal!r}")
+        if 'gain' in goal:
+            _check_gain(mode != L.WALKING_DISCRETE, size_reward)
+            Q.load()
+        held = None
+        if goal:
+            G.load()
+            held = G.outputs(N, ('align', 'fit') + tuple(k for k in ('want', 'todo') if k in goal) +
+                             (('gain', 'ends') if 'gain' in goal else ()), dev)
         # obs['action_mask'] (action_mask=True): rewritten by every reset / step, and by whatever else moves the state
-        self._follow_with(pov, z((N, Q.ACTIONS), torch.uint8) if action_mask else None)
+        self._follow_with(pov, z((N, Q.ACTIONS), torch.uint8) if action_mask else None, held)
 
     def _make_views(self):
         """The observation / result tensors of the env protocol (env.py:281-303) and the per-env task row / episode
@@ -950,7 +1016,8 @@ class SubBatch(_Rows):
         sl = self._sl
         for k in self._VIEWS:
             setattr(self, k, getattr(parent, k)[sl])
-        self._follow_with(parent._pov and parent._pov.rows(sl), None if parent._mask is None else parent._mask[sl])
+        self._follow_with(parent._pov and parent._pov.rows(sl), None if parent._mask is None else parent._mask[sl],
+                          None if parent._goal is None else {k: t[sl] for k, t in parent._goal.items()})
         if parent in parent._fill.drawn:   # (a sub-batch of a batch whose stacks are current starts with them)
             parent._fill.lowered(self)
         self._inherit_sampling()
@@ -1029,6 +1096,37 @@ def _mask_rows(env, out, look, sample, stream, alloc_stream=None):
     agent, _, occ = env._rows
     return Q.launch(agent, occ, env.num_envs, env.select_and_place, out, look, sample, env.env_index_base, env.device,
                     stream, alloc_stream)
+
+
+def _check_gain(other_space, size_reward):
+    if other_space:
+        raise ValueError('goal: gain is defined for the Discrete(18) walking action space only (the action mask it is '
+                         'built on is)')
+    if size_reward:
+        raise ValueError('goal: gain predicts the reward of the env itself; with size_reward=True the step returns '
+                         "SizeReward's (make the env with size_reward=False)")
+
+
+def _goal_rows(env, names, out, stream, alloc_stream=None, captured=False):
+    """One igw_goal launch (goal.launch) over the state rows of a whole VecGridWorld or of a SubBatch; with gain the two
+    igw_action_mask launches in front of it (_Rows.goal).  `captured`: the launch is part of a capture on `stream`,
+    which then is torch's current stream; otherwise the torch work goes to the range's stream."""
+    root, sl, cfg, mask, look = env._root(), env._sl, env.cfg, None, None
+    agent, _, occ = env._rows
+    if 'gain' in names:
+        _check_gain(env.flying or env.walk_dict, cfg.size_reward)
+        mask, look, full, spare = env._goal_scratch()
+        ask = lambda ag, m, lk: Q.action_mask_into(ag.data_ptr(), occ.data_ptr(), env.num_envs,  # noqa: E731
+                                                   env.select_and_place, m.data_ptr(), lk, None, 0, 0, 0, stream)
+        ask(agent, mask, None)
+        with torch.cuda.stream(None if captured else env.stream):
+            full.copy_(agent, non_blocking=True)
+            full.view(torch.int16)[:, 24:30].fill_(20)
+        ask(full, spare, look.data_ptr())
+    state = [root.grid_buf[sl], root.hist_buf[sl], root.aux_buf[sl], agent, root.task_target, root.task_start,
+             root.task_meta, root.task_index]
+    return G.launch(state, env.num_envs, (cfg.right_placement_scale, cfg.wrong_placement_scale, cfg.max_steps,
+                                          cfg.select_and_place), mask, look, names, out, env.device, stream, alloc_stream)
 
 
 def task_eval(targets, grids, full_grids=None, invariant=None, device='cuda:0'):
