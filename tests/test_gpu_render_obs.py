@@ -6,10 +6,12 @@ import numpy as np
 import pytest
 import torch
 
+import large_cases as LC
 import obs_cases as OC
 import obs_model as OM
 
 pytestmark = pytest.mark.gpu
+R_CHUNK, R_SINK_SLOTS = LC.CHUNK, LC.SINK_SLOTS     # pixels per block, slots of the no-frame sink (from the sources)
 
 
 def _env(n=OC.N, autoreset=True, size=(64, 64), **kw):
@@ -109,12 +111,10 @@ def test_dtypes_and_planes(kw):
     assert restarts.any() and not restarts.all()
 
 
-@pytest.mark.parametrize('size', [(13, 7), (1, 1), (96, 80), (64, 64)], ids=lambda s: f'{s[0]}x{s[1]}')
-@pytest.mark.parametrize('kw', [dict(gray=True, stack=2), dict(dtype=torch.float16, stack=2, scale=1 / 255)],
-                         ids=['grey-u8-k2', 'rgb-f16-k2'])
-def test_shapes_that_reach_the_tail_paths(size, kw):
+def _slices_and_sentinels(size, kw, with_frame=True):
     """N = 3, so env bases are odd multiples of the frame; `out` starts 5 elements into a sentinel-filled tensor, so no
-    row of it is aligned for four pixels: heads, bodies and tails, and nothing outside the slice."""
+    row of it is aligned for four pixels: heads, bodies and tails, and nothing outside the slice.  with_frame=False
+    passes frame=None, so that the entry gets out = NULL and the frame's flush goes to the sink."""
     from gridworld_amd import ObsSpec
     spec = ObsSpec(**kw)
     env, actions = _env(3, size=size)
@@ -127,12 +127,13 @@ def test_shapes_that_reach_the_tail_paths(size, kw):
     for flat, lo in ((big, pad), (aligned, 0)):
         out = flat[lo:lo + numel].view(shape)
         env.reset()
-        frame = torch.empty((3, size[1], size[0], 3), dtype=torch.uint8, device=env.device)
+        frame = torch.empty((3, size[1], size[0], 3), dtype=torch.uint8, device=env.device) if with_frame else None
         got = env.render_pov_obs(spec, out=out, fill=True, frame=frame)
         assert got is out
         want = OM.observe(env.render_pov(), None, None, spec)
         _same(out, want, 'fill')
-        assert torch.equal(frame, env.render_pov())
+        if with_frame:
+            assert torch.equal(frame, env.render_pov())
         env.step(actions[0])
         env.render_pov_obs(spec, out=out)
         want = OM.observe(env.render_pov(), want, None, spec)
@@ -147,6 +148,74 @@ def test_shapes_that_reach_the_tail_paths(size, kw):
             assert torch.equal(OM.bits(flat[:pad]), OM.bits(edge)) and torch.equal(OM.bits(flat[-pad:]), OM.bits(edge))
     new = env.render_pov_obs(spec)                                     # no out: a new, filled tensor
     _same(new, OM.observe(env.render_pov(), None, None, spec), 'new')
+
+
+TAIL_SPECS = dict(argvalues=[dict(gray=True, stack=2), dict(dtype=torch.float16, stack=2, scale=1 / 255)],
+                  ids=['grey-u8-k2', 'rgb-f16-k2'])
+
+
+@pytest.mark.parametrize('size', [(13, 7), (1, 1), (96, 80), (64, 64)], ids=lambda s: f'{s[0]}x{s[1]}')
+@pytest.mark.parametrize('kw', **TAIL_SPECS)
+def test_shapes_that_reach_the_tail_paths(size, kw):
+    _slices_and_sentinels(size, kw)
+
+
+@pytest.mark.parametrize('size,with_frame', [((96, 80), False), ((65, 65), False), ((65, 65), True)],
+                         ids=['96x80-no-frame', '65x65-no-frame', '65x65-frame'])
+@pytest.mark.parametrize('kw', **TAIL_SPECS)
+def test_several_chunks_without_a_frame_and_off_four_pixels(size, with_frame, kw):
+    """Two chunks per frame.  Without a frame the second chunk's flush is aimed at sink + slot * 12288 - c0 * 3 with
+    c0 = 4,096; at 65 x 65 = 4,225 pixels the planes of the stack are not aligned alike, so every pixel goes alone."""
+    assert size[0] * size[1] > R_CHUNK and (size == (96, 80) or size[0] * size[1] % 4)
+    _slices_and_sentinels(size, kw, with_frame)
+
+
+def test_without_a_frame_blocks_share_sink_slots():
+    """pov_frame=False on 2,500 envs at 64 x 64: one block per env, more blocks than the sink has slots, so blocks in
+    flight flush their frames over one another's slot.  The observation does not come from there: it equals that of an
+    env that draws the frame too, and the model's."""
+    from gridworld_amd import ObsSpec, VecGridWorld
+    n, spec = 2500, ObsSpec(gray=True, stack=4)
+    assert n > R_SINK_SLOTS
+    targets, poses, actions = OC.inputs()
+    rows = np.arange(n) % OC.N
+    poses = poses[rows].copy()
+    poses[:, 3] += 5.0 * (np.arange(n) // OC.N)                     # no two envs draw the same frame
+    envs = []
+    for kw in (dict(), dict(pov_frame=False)):
+        env = VecGridWorld(n, autoreset=True, max_steps=OC.MAX_STEPS, render_size=(64, 64), renderer='hip', pov_obs=spec,
+                           **kw)
+        env.set_tasks(targets[rows], init_pose=poses)
+        envs.append(env)
+    both, alone = envs
+    acts = torch.from_numpy(np.ascontiguousarray(actions[:, rows])).to(both.device)
+    a, b = both.reset(), alone.reset()
+    assert 'pov' not in b and alone.pov is None
+    stack = OM.observe(a['pov'], None, None, spec)
+    for t in range(4):
+        _same(b['pov_obs'], a['pov_obs'], f'step {t}: without a frame')
+        _same(a['pov_obs'], stack, f'step {t}: the model')
+        if t < 3:
+            a, b = both.step(acts[t])[0], alone.step(acts[t])[0]
+            stack = OM.observe(a['pov'], stack, both.done.clone(), spec)
+    frames = a['pov'].flatten(1)
+    assert frames[OC.N:].ne(frames[:-OC.N]).any(1).float().mean().item() > 0.9   # (the tiled rows do differ)
+
+
+@pytest.mark.parametrize('K', [5, 6, 7, 8])
+@pytest.mark.parametrize('kw', [dict(gray=True), dict(dtype=torch.float16, scale=1 / 255)], ids=['grey-u8', 'rgb-f16'])
+def test_stack_depths_five_to_eight(K, kw):
+    """The shift holds slots 1..7 in seven hand-named registers; the other tests stop at K = 4.  A fill and K + 1
+    shifts without a restart (autoreset=False), so that every slot has held every position."""
+    from gridworld_amd import ObsSpec
+    spec = ObsSpec(stack=K, **kw)
+    env, actions = _env(8, autoreset=False, pov_obs=spec)
+    stack, restarts = _follow(env, actions, spec, K + 1)
+    P = spec.planes
+    assert stack.shape == (8, K * P, 64, 64)
+    slots = stack.reshape(8, K, -1)
+    for k in range(K - 1):                                             # K different frames in most rows
+        assert slots[:, k].ne(slots[:, k + 1]).any(1).float().mean().item() >= 0.5, k
 
 
 def test_the_frame_beside_the_observation():
