@@ -11,6 +11,7 @@ import subprocess
 import numpy as np
 
 import jpeg_model as J
+import value_cases as V
 from render_checks import LLVM
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -100,6 +101,33 @@ def _run(exe, tmp_path, frames, quality, stride):
     return np.fromfile(out, np.uint8).reshape(n, stride), np.fromfile(sz, np.int32)
 
 
+def _check(out, sizes, want, stride, what):
+    for i in range(len(want)):
+        if len(want[i]) <= stride:
+            assert sizes[i] == len(want[i]), what + (i,)
+            assert out[i, :sizes[i]].tobytes() == want[i], what + (i,)
+            assert (out[i, sizes[i]:] == GUARD).all(), what + (i,)
+        else:
+            assert sizes[i] == -len(want[i]) and out[i].tobytes() == want[i][:stride], what + (i,)
+
+
+def test_the_kernel_source_on_the_host_equals_the_model_on_every_code_and_at_the_window_boundary(tmp_path):
+    """The frames of tests/value_cases.py (pinned by tests/test_value_cases_cpu.py): nearly every AC symbol of both
+    tables, 26-bit codes, ZRL chains, blocks without an EOB, every DC category, and the scans that end, or whose chunk
+    ends, on the window's last bit.  The three window frames also with a stride a few bytes short of the stream, so
+    that the stride guard crosses the aligned flush.  (All of them together take the emulation about ten seconds.)"""
+    from gridworld_amd import codec as K
+    exe = _build(tmp_path)
+    for name, frames, q in V.jpeg_batches():
+        want = V.jpeg_streams(name)
+        strides = [K.jpeg_bound(frames.shape[2], frames.shape[1])]
+        if name in V.aligned():
+            strides += [len(want[0]) - 1, len(want[0]) - 5]
+        for st in strides:
+            out, sizes = _run(exe, tmp_path, np.ascontiguousarray(frames), q, st)
+            _check(out, sizes, want, st, (name, q, st))
+
+
 def test_the_kernel_source_on_the_host_equals_the_model(tmp_path):
     from gridworld_amd import codec as K
     exe = _build(tmp_path)
@@ -120,11 +148,4 @@ def test_the_kernel_source_on_the_host_equals_the_model(tmp_path):
         st = stride or K.jpeg_bound(f.shape[2], f.shape[1])
         for q in qualities:
             out, sizes = _run(exe, tmp_path, f, q, st)
-            for i in range(len(f)):
-                want = J.encode(f[i], q)
-                if len(want) <= st:
-                    assert sizes[i] == len(want), (what, q, i)
-                    assert out[i, :sizes[i]].tobytes() == want, (what, q, i)
-                    assert (out[i, sizes[i]:] == GUARD).all(), (what, q, i)
-                else:
-                    assert sizes[i] == -len(want) and out[i].tobytes() == want[:st], (what, q, i)
+            _check(out, sizes, [J.encode(x, q) for x in f], st, (what, q))
