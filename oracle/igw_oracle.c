@@ -90,6 +90,181 @@ struct igo_env {
 
 static inline int cell(int y, int x, int z) { return (y * IGO_GRID_X + x) * IGO_GRID_Z + z; }
 
+/* ---------------------------------------------------------------- census
+ * Situation counters of the step path (tests/step_census.py).  Compiled in with -DIGO_CENSUS only;
+ * without it every CENSUS_* line below is empty and the object code is that of the plain build.
+ * Everything that counts lives in census_* functions of its own, so that a --coverage build of the
+ * step path's functions sees calls there, never extra branches.  Single-threaded use only. */
+#ifdef IGO_CENSUS
+#include <stdio.h>
+enum {
+    CB_HIT_FACE = 0,                       /* [6 sides of the hit block][block y -1..7] */
+    CB_HIT_DIAGONAL = CB_HIT_FACE + 54,    /* previous key differs from the block in more than one coordinate */
+    CB_HIT_FIRST_SAMPLE,                   /* the ray starts inside a solid cell: previous is None */
+    CB_HIT_GROUND_IN, CB_HIT_GROUND_OUT,   /* ground plane under the build zone / around it */
+    CB_HIT_NONE,
+    CB_RAY_STARTS_OUTSIDE, CB_RAY_ENTERS, CB_RAY_LEAVES, CB_RAY_REENTERS,
+    CB_TIE_HIT_POS, CB_TIE_HIT_NEG, CB_TIE_COLLIDE_POS, CB_TIE_COLLIDE_NEG,
+    CB_COLLIDE,                            /* [6 FACES][body height 0 = head, 1 = legs] */
+    CB_LAND_BLOCK = CB_COLLIDE + 12, CB_LAND_GROUND, CB_HEAD_BUMP,
+    CB_PLACE_OK,                           /* [grid level 0..8] */
+    CB_PLACE_REFUSED_SIDE = CB_PLACE_OK + 9, /* x<-5, x>5, z<-5, z>5, y<-1, y>=8 */
+    CB_PLACE_REFUSED_EMPTY = CB_PLACE_REFUSED_SIDE + 6, CB_PLACE_REFUSED_NEGATIVE, CB_PLACE_REFUSED_BODY,
+    CB_PLACE_NOTHING_HIT,
+    CB_BREAK_OK,                           /* [grid level 0..8] */
+    CB_BREAK_GROUND = CB_BREAK_OK + 9, CB_BREAK_START_BLOCK, CB_BREAK_STANDING_ON, CB_FALL_AFTER_BREAK,
+    CB_BREAK_NOTHING_HIT,
+    CB_AGENT_IN_ZONE, CB_AGENT_RING,       /* the agent's cell after a step: in the zone / in the padding ring */
+    CB_AGENT_BEYOND,                       /* [x<-6, x>6, z<-6, z>6] */
+    CB_AGENT_ABOVE = CB_AGENT_BEYOND + 4, CB_AGENT_BELOW, CB_AGENT_OFF_GROUND, CB_AGENT_TERMINAL_VELOCITY,
+    CB_COUNT
+};
+static int64_t census[CB_COUNT];
+static const void* census_fall_env; /* env whose supporting block was just broken */
+
+void igo_census_reset(void) { memset(census, 0, sizeof(census)); census_fall_env = NULL; }
+int igo_census_read(int64_t* out) {
+    if (out) memcpy(out, census, sizeof(census));
+    return CB_COUNT;
+}
+/* bin names, one per line, in index order */
+const char* igo_census_names(void) {
+    static char buf[8192];
+    static const char* side[6] = {"top", "bottom", "xlo", "xhi", "zlo", "zhi"};
+    static const char* face[6] = {"up", "down", "xneg", "xpos", "zpos", "zneg"};
+    static const char* wall[6] = {"xlo", "xhi", "zlo", "zhi", "floor", "ceiling"};
+    char* p = buf;
+    for (int f = 0; f < 6; f++)
+        for (int y = -1; y < 8; y++) p += sprintf(p, "hit.%s.level%d\n", side[f], y);
+    p += sprintf(p, "hit.diagonal\nhit.first_sample\nhit.ground_in_zone\nhit.ground_outside\nhit.nothing\n"
+                    "ray.starts_outside_zone\nray.enters_zone\nray.leaves_zone\nray.reenters_zone\n"
+                    "tie.hit_sample.positive\ntie.hit_sample.negative\ntie.position.positive\ntie.position.negative\n");
+    for (int f = 0; f < 6; f++) p += sprintf(p, "collide.%s.head\ncollide.%s.legs\n", face[f], face[f]);
+    p += sprintf(p, "land.block\nland.ground\nhead_bump\n");
+    for (int y = 0; y < 9; y++) p += sprintf(p, "place.level%d\n", y);
+    for (int w = 0; w < 6; w++) p += sprintf(p, "place.refused.%s\n", wall[w]);
+    p += sprintf(p, "place.refused.empty_slot\nplace.refused.negative_slot\nplace.refused.own_body\nplace.nothing_hit\n");
+    for (int y = 0; y < 9; y++) p += sprintf(p, "break.level%d\n", y);
+    p += sprintf(p, "break.ground\nbreak.start_block\nbreak.standing_on\nbreak.fall_after\nbreak.nothing_hit\n");
+    p += sprintf(p, "agent.in_zone\nagent.padding_ring\nagent.beyond.xlo\nagent.beyond.xhi\nagent.beyond.zlo\n"
+                    "agent.beyond.zhi\nagent.above_level8\nagent.below_level-4\nagent.off_ground_plane\n"
+                    "agent.terminal_velocity\n");
+    return buf;
+}
+#ifdef IGO_CENSUS_GCOV
+extern void __gcov_dump(void);
+extern void __gcov_reset(void);
+/* writes the branch counts of this library to its .gcda now (and starts counting from zero: gcov merges the files) */
+void igo_census_flush(void) { __gcov_dump(); __gcov_reset(); }
+#endif
+static int census_in_zone(const int* k) {
+    return k[0] >= -5 && k[0] <= 5 && k[2] >= -5 && k[2] <= 5 && k[1] >= -1 && k[1] < 8;
+}
+static void census_ties(const double* p, int pos_bin) {
+    for (int i = 0; i < 3; i++)
+        if (p[i] - floor(p[i]) == 0.5) census[pos_bin + (p[i] < 0)]++;
+}
+/* one sample of the ray; st[0]: samples seen, st[1]: the last one was inside the zone, st[2]: the ray has left it */
+static void census_ray(const double* p, const int* key, int* st) {
+    int in = census_in_zone(key);
+    census_ties(p, CB_TIE_HIT_POS);
+    if (st[0] == 0 && !in) census[CB_RAY_STARTS_OUTSIDE]++;
+    if (st[0] > 0 && in && !st[1]) census[st[2] ? CB_RAY_REENTERS : CB_RAY_ENTERS]++;
+    if (st[0] > 0 && !in && st[1]) { census[CB_RAY_LEAVES]++; st[2] = 1; }
+    st[1] = in;
+    st[0]++;
+}
+static void census_hit(const int* block, const int* prev, int hp) {
+    if (block[1] == -2) {
+        census[block[0] >= -5 && block[0] <= 5 && block[2] >= -5 && block[2] <= 5 ? CB_HIT_GROUND_IN : CB_HIT_GROUND_OUT]++;
+        return;
+    }
+    if (!hp) { census[CB_HIT_FIRST_SAMPLE]++; return; }
+    int d[3] = {prev[0] - block[0], prev[1] - block[1], prev[2] - block[2]};
+    int f = -1;
+    if (d[0] == 0 && d[2] == 0 && d[1] == 1) f = 0;
+    else if (d[0] == 0 && d[2] == 0 && d[1] == -1) f = 1;
+    else if (d[1] == 0 && d[2] == 0 && d[0] == -1) f = 2;
+    else if (d[1] == 0 && d[2] == 0 && d[0] == 1) f = 3;
+    else if (d[0] == 0 && d[1] == 0 && d[2] == -1) f = 4;
+    else if (d[0] == 0 && d[1] == 0 && d[2] == 1) f = 5;
+    if (f < 0) census[CB_HIT_DIAGONAL]++;
+    else census[CB_HIT_FACE + f * 9 + block[1] + 1]++;
+}
+static void census_collide(int f, int dy, const int* op) {
+    census[CB_COLLIDE + 2 * f + dy]++;
+    if (f == 0) census[CB_HEAD_BUMP]++;
+    if (f == 1) census[op[1] == -2 ? CB_LAND_GROUND : CB_LAND_BLOCK]++;
+}
+/* called before the place is decided; states the decision of place_or_remove_block again */
+static void census_place(const igo_env* e, int hit, int have_prev, const int* previous) {
+    if (!(hit && have_prev)) { census[CB_PLACE_NOTHING_HIT]++; return; }
+    int inv = e->inventory[e->active_block - 1];
+    if (inv <= 0) { census[inv == 0 ? CB_PLACE_REFUSED_EMPTY : CB_PLACE_REFUSED_NEGATIVE]++; return; }
+    int w = previous[0] < -5 ? 0 : previous[0] > 5 ? 1 : previous[2] < -5 ? 2 : previous[2] > 5 ? 3
+          : previous[1] < -1 ? 4 : previous[1] >= 8 ? 5 : -1;
+    if (w >= 0) { census[CB_PLACE_REFUSED_SIDE + w]++; return; }
+    double x = e->pos[0], y = e->pos[1] - (PLAYER_HEIGHT - 1) + AGENT_PAD, z = e->pos[2];
+    double bx = previous[0] - 0.5, by = previous[1], bz = previous[2] - 0.5;
+    int body = bx <= x && x <= bx + 1 && bz <= z && z <= bz + 1 &&
+               ((by <= y && y <= by + 1) || (by <= (y + 1) && (y + 1) <= by + 1));
+    census[body ? CB_PLACE_REFUSED_BODY : CB_PLACE_OK + previous[1] + 1]++;
+}
+static void census_break(const igo_env* e, int remove, int hit, const int* block) {
+    if (!remove) return;
+    if (!hit) { census[CB_BREAK_NOTHING_HIT]++; return; }
+    int texture = block[1] == -2 ? GREY : e->grid[cell(block[1] + 1, block[0] + 5, block[2] + 5)];
+    if (texture == GREY || texture == WHITE) { census[CB_BREAK_GROUND]++; return; }
+    int np[3] = {(int)rint(e->pos[0]), (int)rint(e->pos[1]), (int)rint(e->pos[2])};
+    census[CB_BREAK_OK + block[1] + 1]++;
+    if (e->init[cell(block[1] + 1, block[0] + 5, block[2] + 5)] != 0) census[CB_BREAK_START_BLOCK]++;
+    if (block[0] == np[0] && block[2] == np[2] && block[1] == np[1] - 2 && e->dy == 0) {
+        census[CB_BREAK_STANDING_ON]++;
+        census_fall_env = e;
+    }
+}
+static void census_fall(const igo_env* e, double y_before) {
+    if (census_fall_env != e) return;
+    census_fall_env = NULL;
+    if (e->pos[1] < y_before) census[CB_FALL_AFTER_BREAK]++;
+}
+static void census_agent(const igo_env* e) {
+    int k[3] = {(int)rint(e->pos[0]), (int)rint(e->pos[1]), (int)rint(e->pos[2])};
+    int ax = abs(k[0]), az = abs(k[2]), m = ax > az ? ax : az;
+    if (census_in_zone(k)) census[CB_AGENT_IN_ZONE]++;
+    if (m == 6) census[CB_AGENT_RING]++;
+    if (k[0] < -6) census[CB_AGENT_BEYOND + 0]++;
+    if (k[0] > 6) census[CB_AGENT_BEYOND + 1]++;
+    if (k[2] < -6) census[CB_AGENT_BEYOND + 2]++;
+    if (k[2] > 6) census[CB_AGENT_BEYOND + 3]++;
+    if (k[1] > 7) census[CB_AGENT_ABOVE]++;
+    if (k[1] < -4) census[CB_AGENT_BELOW]++;
+    if (fabs(e->pos[0]) > 18.5 || fabs(e->pos[2]) > 18.5) census[CB_AGENT_OFF_GROUND]++;
+    if (e->dy == -TERMINAL_VELOCITY) census[CB_AGENT_TERMINAL_VELOCITY]++;
+}
+#define CENSUS_AGENT(e) census_agent(e);
+#define CENSUS_RAY_STATE int census_st[3] = {0, 0, 0};
+#define CENSUS_RAY(p, key) census_ray(p, key, census_st);
+#define CENSUS_HIT(block, prev, hp) census_hit(block, prev, hp);
+#define CENSUS_NO_HIT census[CB_HIT_NONE]++;
+#define CENSUS_POSITION_TIES(p) census_ties(p, CB_TIE_COLLIDE_POS);
+#define CENSUS_COLLIDE(f, dy, op) census_collide(f, dy, op);
+#define CENSUS_PLACE(e, hit, hp, prev) census_place(e, hit, hp, prev);
+#define CENSUS_BREAK(e, remove, hit, block) census_break(e, remove, hit, block);
+#define CENSUS_FALL(e, y) census_fall(e, y);
+#else
+#define CENSUS_RAY_STATE
+#define CENSUS_RAY(p, key)
+#define CENSUS_HIT(block, prev, hp)
+#define CENSUS_NO_HIT
+#define CENSUS_POSITION_TIES(p)
+#define CENSUS_COLLIDE(f, dy, op)
+#define CENSUS_PLACE(e, hit, hp, prev)
+#define CENSUS_BREAK(e, remove, hit, block)
+#define CENSUS_FALL(e, y)
+#define CENSUS_AGENT(e)
+#endif
+
 /* ------------------------------------------------------------------ Task */
 
 /* tasks/task.py:9-72 */
@@ -265,15 +440,18 @@ static int hit_test(const igo_env* e, const double* position, const double* vect
     double x = position[0], y = position[1], z = position[2];
     double dx = vector[0], dy = vector[1], dz = vector[2];
     int prev[3] = {0, 0, 0}, hp = 0;
+    CENSUS_RAY_STATE
     for (int it = 0; it < max_distance * m; it++) {
         double p[3] = {x, y, z};
         int key[3], col;
         normalize(p, key);
+        CENSUS_RAY(p, key)
         int differs = !hp || key[0] != prev[0] || key[1] != prev[1] || key[2] != prev[2];
         if (differs && world_lookup(e, key[0], key[1], key[2], &col)) {
             block[0] = key[0]; block[1] = key[1]; block[2] = key[2];
             previous[0] = prev[0]; previous[1] = prev[1]; previous[2] = prev[2];
             *have_prev = hp;
+            CENSUS_HIT(block, prev, hp)
             return 1;
         }
         prev[0] = key[0]; prev[1] = key[1]; prev[2] = key[2];
@@ -281,6 +459,7 @@ static int hit_test(const igo_env* e, const double* position, const double* vect
         x = x + dx / m; y = y + dy / m; z = z + dz / m;
     }
     *have_prev = 0;
+    CENSUS_NO_HIT
     return 0;
 }
 
@@ -327,6 +506,7 @@ static void collide(igo_env* e, const double* position, int height, double* out)
     double p[3] = {position[0], position[1], position[2]};
     int np[3];
     normalize(position, np);
+    CENSUS_POSITION_TIES(position)
     for (int f = 0; f < 6; f++) {
         const int* face = FACES[f];
         for (int i = 0; i < 3; i++) {
@@ -338,6 +518,7 @@ static void collide(igo_env* e, const double* position, int height, double* out)
                 op[1] -= dy;
                 op[i] += face[i];
                 if (!world_lookup(e, op[0], op[1], op[2], &col)) continue;
+                CENSUS_COLLIDE(f, dy, op)
                 p[i] -= (d - pad) * face[i];
                 if (f == 0 || f == 1) e->dy = 0; /* ground or ceiling: stop falling / rising */
                 break;
@@ -373,6 +554,7 @@ static void update_substep(igo_env* e, double dt) {
         collide(e, c2, PLAYER_HEIGHT, res);
     }
     e->pos[0] = res[0]; e->pos[1] = res[1]; e->pos[2] = res[2];
+    CENSUS_FALL(e, y)
 }
 
 /* core/world.py:203-220 (sustain is always False for the env, env.py:32) */
@@ -398,6 +580,7 @@ static void place_or_remove_block(igo_env* e, int remove, int place) {
     get_sight_vector(e, vector);
     int hit = hit_test(e, e->pos, vector, block, previous, &have_prev);
     if (place) {
+        CENSUS_PLACE(e, hit, have_prev, previous)
         if (hit && have_prev) {
             if (e->inventory[e->active_block - 1] > 0 &&
                 build_zone(previous[0], previous[1], previous[2], 0)) {
@@ -414,6 +597,7 @@ static void place_or_remove_block(igo_env* e, int remove, int place) {
             }
         }
     }
+    CENSUS_BREAK(e, remove, hit, block)
     if (remove && hit) {
         int texture = 0;
         world_lookup(e, block[0], block[1], block[2], &texture);
@@ -515,6 +699,7 @@ void igo_reset(igo_env* e) {
 static void finish_step(igo_env* e) {
     int8_t syn[IGO_CELLS];
     int right, wrong, done;
+    CENSUS_AGENT(e)
     for (int i = 0; i < 6; i++) e->obs_inventory[i] = (float)e->inventory[i];
     e->obs_compass = (float)(e->rot[0] - 180.);
     e->obs_agentPos[0] = (float)e->pos[0];

@@ -161,7 +161,9 @@ class LogChecker:
             self.checked += 1
 
 
-def run_case(c, rng):
+def draw_case(c, rng):
+    """The scenario of case c: every draw run_case makes before its step loop, in its order, and nothing of the GPU
+    side (tests/test_step_census_cpu.py runs the same scenarios on the oracle alone)."""
     n = int(rng.choice([1, 3, 15, 16, 17, 63, 64, 65, 200, 777, 1500, 4097]))
     gs = int(rng.choice([0, 64, 32, 16, 8, 4, 2, 1]))
     mode = str(rng.choice(['walking', 'flying', 'walking_dict'], p=[0.5, 0.3, 0.2]))
@@ -200,6 +202,42 @@ def run_case(c, rng):
     desc = (f'case {c}: n={n} gs={gs} {mode} autoreset={autoreset} start={with_start} dense={dense} full_grid={fg is not None} '
             f'poses={poses is not None} extra={extra} tasks={ntasks} host_resets={host_resets} split={split} snapshot={snapshot} {kw}')
     space = dict(action_space='flying') if mode == 'flying' else dict(discretize=False) if mode == 'walking_dict' else {}
+    samp_seed = int(rng.randint(1 << 30))
+    rk = None
+    if extra == 'random_tasks':
+        rk = dict(max_blocks=int(rng.randint(1, 9)), height_levels=int(rng.randint(1, 4)), max_dist=int(rng.randint(1, 4)),
+                  num_colors=int(rng.randint(1, 7)))
+        desc += f' {rk}'
+    n_logged = cap = None
+    if logging:
+        n_logged = int(min(n, rng.choice([1, 3, 8])))
+        cap = int(rng.choice([kw['max_steps'], max(1, kw['max_steps'] // 2), 5]))
+    return dict(n=n, gs=gs, mode=mode, kw=kw, autoreset=autoreset, with_start=with_start, T=T, dense=dense, extra=extra,
+                sampling=sampling, logging=logging, ntasks=ntasks, tg=tg, st=st, fg=fg, poses=poses, manual=manual,
+                host_resets=host_resets, fused=fused, split=split, snapshot=snapshot, desc=desc, space=space,
+                samp_seed=samp_seed, rk=rk, n_logged=n_logged, cap=cap)
+
+
+def draw_steps(case, rng):
+    """The action draws of the case's step loop, in run_case's order: ('chunk', int32 [k, n]) for the fused replay,
+    ('step', device-side actions, oracle-side actions) for single steps."""
+    n, T, mode = case['n'], case['T'], case['mode']
+    t = 0
+    while case['fused'] and t < T:
+        chunk = rng.choice(18, size=(int(rng.choice([1, 7, 30])), n), p=WALK_W / WALK_W.sum()).astype(np.int32)
+        yield 'chunk', chunk, None
+        t += len(chunk)
+    for t in range(0 if not case['fused'] else T, T):
+        da, oa = draw_actions(rng, mode, n)
+        yield 'step', da, oa
+
+
+def run_case(c, rng):
+    case = draw_case(c, rng)
+    (n, gs, mode, kw, autoreset, T, extra, sampling, logging, ntasks, tg, st, fg, poses, manual, host_resets, fused, split,
+     snapshot, desc, space, samp_seed, rk) = (case[k] for k in (
+         'n', 'gs', 'mode', 'kw', 'autoreset', 'T', 'extra', 'sampling', 'logging', 'ntasks', 'tg', 'st', 'fg', 'poses',
+         'manual', 'host_resets', 'fused', 'split', 'snapshot', 'desc', 'space', 'samp_seed', 'rk'))
     mk = lambda: VecGridWorld(n, autoreset=autoreset, lanes_per_env=gs, num_tasks=ntasks, **space, **kw)  # noqa: E731
     env = mk()
     ob = O.OracleBatch(n, **space, **kw)
@@ -219,21 +257,15 @@ def run_case(c, rng):
                 if poses is not None:
                     ob.envs[e].set_initial_pose(poses[et[e]])
 
-    samp_seed = int(rng.randint(1 << 30))
     if extra == 'random_tasks':
-        rk = dict(max_blocks=int(rng.randint(1, 9)), height_levels=int(rng.randint(1, 4)), max_dist=int(rng.randint(1, 4)),
-                  num_colors=int(rng.randint(1, 7)))
         env.set_random_tasks(True, seed=samp_seed, **rk)
-        desc += f' {rk}'
     else:
         env.set_tasks(tg, st, full_grids=fg, init_pose=poses, env_task=np.zeros(n, np.int32) if sampling else None)
         if sampling:
             env.set_task_sampling(True, seed=samp_seed)
     checker = None
     if logging:
-        n_logged = int(min(n, rng.choice([1, 3, 8])))
-        cap = int(rng.choice([kw['max_steps'], max(1, kw['max_steps'] // 2), 5]))
-        checker = LogChecker(env, ob, n_logged, cap, desc)
+        checker = LogChecker(env, ob, case['n_logged'], case['cap'], desc)
     env.reset()
     torch.cuda.synchronize()
     if manual:
@@ -249,8 +281,9 @@ def run_case(c, rng):
     try:
         O.use_device_trig(mode != 'walking' or poses is not None)
         t = 0
+        steps = draw_steps(case, rng)
         while fused and t < T:
-            chunk = rng.choice(18, size=(int(rng.choice([1, 7, 30])), n), p=WALK_W / WALK_W.sum()).astype(np.int32)
+            _, chunk, _ = next(steps)
             rw, dn = env.rollout_actions(torch.as_tensor(chunk), return_rewards=True)
             torch.cuda.synchronize()
             rw, dn = rw.cpu().numpy(), dn.cpu().numpy()
@@ -270,7 +303,7 @@ def run_case(c, rng):
                     env.set_task_sampling(True, seed=samp_seed, n_tasks=ntasks)
                 elif extra == 'random_tasks':
                     env.set_random_tasks(True, seed=samp_seed, **rk)
-            da, oa = draw_actions(rng, mode, n)
+            _, da, oa = next(steps)
             if subs:
                 a = da.to(env.device)
                 h = n // 2

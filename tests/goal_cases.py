@@ -62,20 +62,18 @@ def env_truth(target, start, grid, cached):
             np.array([ev['max_int'], ev['target_size'], np.count_nonzero(s), cached], np.int16), want, todo)
 
 
-@functools.lru_cache(None)
-def truth(name):
-    """dict of read-only arrays over [checkpoint, env]: align int8 [C, E, 3], fit int16 [C, E, 4], want / todo int8
+def truth_of(case, checkpoints=CHECKPOINTS):
+    """dict of arrays (of a case of any number of envs E) over [checkpoint, env]: align int8 [C, E, 3], fit int16 [C, E, 4], want / todo int8
     [C, E, 9, 11, 11], gain float32 [C, E, 18], ends uint8 [C, E, 18]; and for the coverage floors changed bool
     [C, E, 8] (the probe changed the grid) and live float32 [C, E, 8] (what a model that counts the probe's reward from
     the LIVE maximum instead of the cached one would pay)."""
-    case = cases()[name]
-    C = len(CHECKPOINTS)
+    C, E = len(checkpoints), len(case['targets'])
     starts = case['starts'] if case['starts'] is not None else np.zeros_like(case['targets'])
     res = dict(align=np.zeros((C, E, 3), np.int8), fit=np.zeros((C, E, 4), np.int16),
                want=np.zeros((C, E, 9, 11, 11), np.int8), todo=np.zeros((C, E, 9, 11, 11), np.int8),
                gain=np.zeros((C, E, 18), np.float32), ends=np.zeros((C, E, 18), np.uint8),
                changed=np.zeros((C, E, 8), bool), live=np.zeros((C, E, 8), np.float32))
-    for c, tc in enumerate(CHECKPOINTS):
+    for c, tc in enumerate(checkpoints):
         ob = MC.oracle_batch(case, 9)
         for t in range(tc):
             ob.step_walking(np.tile(case['actions'][t], 9), nthreads=8)
@@ -96,6 +94,13 @@ def truth(name):
                 wrong = state0[i]['syn_prev_size'] - st['syn_prev_size']
                 right = st['syn_max_int'] - int(res['fit'][c, i, 0]) if wrong != 0 else 0
                 res['live'][c, i, j] = np.float32(right * RIGHT if right != 0 else wrong * WRONG)
+    return res
+
+
+@functools.lru_cache(None)
+def truth(name):
+    """truth_of the named case at CHECKPOINTS (read-only, computed once)."""
+    res = truth_of(cases()[name])
     for v in res.values():
         v.setflags(write=False)
     return res

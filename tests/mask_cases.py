@@ -107,9 +107,9 @@ def cases():
 
 
 def oracle_batch(case, blocks=1):
-    """An OracleBatch of `blocks` copies of the case's E envs, reset."""
+    """An OracleBatch of `blocks` copies of the case's envs, reset."""
     from oracle import oracle as O
-    ob = O.OracleBatch(blocks * E, **case['kw'])
+    ob = O.OracleBatch(blocks * len(case['targets']), **case['kw'])
     tile = lambda a: None if a is None else np.concatenate([a] * blocks)  # noqa: E731
     ob.set_tasks(tile(case['targets']), tile(case['starts']))
     if case['poses'] is not None:
@@ -118,13 +118,13 @@ def oracle_batch(case, blocks=1):
     return ob
 
 
-@functools.lru_cache(None)
-def truth(name):
-    """(mask uint8 [C, E, 18], look int16 [C, E, 2]) of the case at its checkpoints, from the oracle alone."""
-    case = cases()[name]
-    masks = np.zeros((len(CHECKPOINTS), E, 18), np.uint8)
-    looks = np.full((len(CHECKPOINTS), E, 2), -1, np.int16)
-    for c, tc in enumerate(CHECKPOINTS):
+def truth_of(case, checkpoints=CHECKPOINTS):
+    """(mask uint8 [C, E, 18], look int16 [C, E, 2]) of a case (of any number of envs E) at the checkpoints, from the
+    oracle alone."""
+    E = len(case['targets'])
+    masks = np.zeros((len(checkpoints), E, 18), np.uint8)
+    looks = np.full((len(checkpoints), E, 2), -1, np.int16)
+    for c, tc in enumerate(checkpoints):
         ob = oracle_batch(case, 9)
         for t in range(tc):
             ob.step_walking(np.tile(case['actions'][t], 9), nthreads=8)
@@ -147,6 +147,13 @@ def truth(name):
             for k in range(1, 7):
                 assert not m[:, 5 + k].any()   # a hotbar action alone never changes the grid
                 m[:, 5 + k] = state[:, 7] != k
+    return masks, looks
+
+
+@functools.lru_cache(None)
+def truth(name):
+    """truth_of the named case at CHECKPOINTS (read-only, computed once)."""
+    masks, looks = truth_of(cases()[name])
     masks.setflags(write=False)
     looks.setflags(write=False)
     return masks, looks
