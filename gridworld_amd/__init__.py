@@ -19,3 +19,5 @@ from . import query  # noqa: F401,E402
 from .query import ACTION_NAMES as action_mask_names  # noqa: F401,E402
 from . import goal  # noqa: F401,E402
 from .goal import goal_world  # noqa: F401,E402
+from . import aim  # noqa: F401,E402
+from .aim import aim_action, aim_decode  # noqa: F401,E402

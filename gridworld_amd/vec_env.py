@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import aim as A
 from . import codec as K
 from . import goal as G
 from . import query as Q
@@ -323,6 +324,22 @@ class _Rows:
             (('gain', 'ends') if gain else ())
         self._in_use(*(out or {}).values())
         res = _goal_rows(self, names, out, self._stream(), self.stream)
+        self._in_use(*res.values())
+        return res
+
+    # ---- which cells a turn of the camera reaches (libigw_aim.so, include/igw_aim.h) ----
+    def aim(self, max_turns=72, place=True, brk=True, out=None):
+        """Which grid cells a place / a break can reach from every env's CURRENT position by turning the camera alone, and
+        the cheapest turn that gets there: a dict of 'place' and 'break' (place=True / brk=True),
+        each int32 [N, 9, 11, 11] -- per cell the code turns << 16 | (dpitch_steps + 36) << 8 | (dyaw_steps + 36) of the
+        cheapest camera direction within `max_turns` (0..72) 5-degree camera actions whose sight ray would fill / clear
+        that cell, -1 where there is none (aim_decode, aim_action).  Inventory and the active block are not looked at.
+        The planes are strided views of 1104-word rows, as `grid` is of its rows.  One igw_aim launch on the range's
+        stream; `out`: a dict of planes to write, as an earlier call returned them; with every plane given nothing is
+        allocated, so the call can be captured.  Discrete(18) walking only: ValueError for flying and Dict-action envs,
+        for a max_turns outside 0..72 and with both planes off."""
+        self._in_use(*(out or {}).values())
+        res = _aim_rows(self, max_turns, place, brk, out, self._stream(), self.stream)
         self._in_use(*res.values())
         return res
 
@@ -1096,6 +1113,15 @@ def _mask_rows(env, out, look, sample, stream, alloc_stream=None):
     agent, _, occ = env._rows
     return Q.launch(agent, occ, env.num_envs, env.select_and_place, out, look, sample, env.env_index_base, env.device,
                     stream, alloc_stream)
+
+
+def _aim_rows(env, max_turns, place, brk, out, stream, alloc_stream=None):
+    """One igw_aim launch (aim.launch) over the state rows of a whole VecGridWorld or of a SubBatch."""
+    if env.flying or env.walk_dict:
+        raise ValueError('aim is defined for the Discrete(18) walking action space only (its turns are that space\'s '
+                         '5-degree camera actions)')
+    agent, _, occ = env._rows
+    return A.launch(agent, occ, env.num_envs, max_turns, place, brk, out, env.device, stream, alloc_stream)
 
 
 def _check_gain(other_space, size_reward):
