@@ -21,3 +21,5 @@ from . import goal  # noqa: F401,E402
 from .goal import goal_world  # noqa: F401,E402
 from . import aim  # noqa: F401,E402
 from .aim import aim_action, aim_decode  # noqa: F401,E402
+from . import peek  # noqa: F401,E402
+from .peek import peek_best, peek_decode  # noqa: F401,E402

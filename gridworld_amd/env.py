@@ -384,6 +384,16 @@ class GridWorld:
             out['ends'] = out['ends'].astype(np.bool_)
         return out
 
+    def peek(self, actions, gamma=1.0):
+        """What this env would be paid, when it would end, what it would build and where it would stand if it played
+        each of the K sequences of H actions `actions` (integers [K, H]) from the state of the last reset / step
+        (VecGridWorld.peek), as numpy: reward float32 [K, H], ends int16 [K], change int16
+        [K, H], pose float32 [K, 5], ret float32 [K].  The env is not moved.  Discrete(18) only."""
+        a = np.asarray(actions)
+        if a.ndim != 2:
+            raise ValueError(f'peek: actions must be [K, H], got shape {a.shape}')
+        return {k: t[0].cpu().numpy() for k, t in self._vec.peek(a, gamma=gamma).items()}
+
     def render(self):
         """Renderer.render() (gridworld/render.py:129-144): the current frame as RGBA uint8 [H, W, 4], row 0 on top."""
         if not self._renders():

@@ -15,6 +15,7 @@ from . import _lib as L
 from . import aim as A
 from . import codec as K
 from . import goal as G
+from . import peek as P
 from . import query as Q
 from . import render as R
 
@@ -340,6 +341,30 @@ class _Rows:
         for a max_turns outside 0..72 and with both planes off."""
         self._in_use(*(out or {}).values())
         res = _aim_rows(self, max_turns, place, brk, out, self._stream(), self.stream)
+        self._in_use(*res.values())
+        return res
+
+    # ---- K action sequences of H steps from the live state (libigw_peek.so, include/igw_peek.h) ----
+    def peek(self, actions, gamma=1.0, outputs=P.OUTPUTS, out=None):
+        """What every env would be paid, when its episode would end, what it would build and where it would stand if it
+        played each of K sequences of H actions from its CURRENT state, which is not touched.
+        `actions`: an integer tensor or array [K, H] (the same sequences for every env) or [N, K, H], 1 <= K <= 4096,
+        1 <= H <= 32; converted to a contiguous int32 device tensor only if it is not one already (a value outside 0..17 of
+        any integer width is a no-op).  A dict of the
+        `outputs` named:
+          reward float32 [N, K, H]   the reward of step h, +0.0 after the candidate ended
+          ends   int16 [N, K]        h + 1 of the step that returned done, 0 if none did
+          change int16 [N, K, H]     colour << 11 | cell of the cell step h changed, -1 for none (peek_decode)
+          pose   float32 [N, K, 5]   agentPos after the last executed step
+          ret    float32 [N, K]      the return discounted by `gamma`, summed in binary64 (peek_best)
+        Every step is bit for bit the step's own; a candidate ends with the first step that returns done and no reset
+        is simulated.  One igw_peek launch on the range's stream; `out`: a dict of tensors to write, as an earlier call
+        returned them; with every output given nothing is allocated, so the call can be captured.  ValueError outside
+        Discrete(18) walking, with size_reward=True (the wrapper's reward is not what is predicted), for K or H out of
+        range, a wrong rank, a first dimension that is not N, and for empty or unknown outputs."""
+        names = P.check_outputs(outputs)
+        self._in_use(*(out or {}).values())
+        res = _peek_rows(self, actions, gamma, names, out, self._stream(), self.stream)
         self._in_use(*res.values())
         return res
 
@@ -1122,6 +1147,40 @@ def _aim_rows(env, max_turns, place, brk, out, stream, alloc_stream=None):
                          '5-degree camera actions)')
     agent, _, occ = env._rows
     return A.launch(agent, occ, env.num_envs, max_turns, place, brk, out, env.device, stream, alloc_stream)
+
+
+def _peek_rows(env, actions, gamma, names, out, stream, alloc_stream=None):
+    """One igw_peek launch (peek.launch) over the state rows of a whole VecGridWorld or of a SubBatch."""
+    if env.flying or env.walk_dict:
+        raise ValueError('peek is defined for the Discrete(18) walking action space only')
+    if env.cfg.size_reward:
+        raise ValueError('peek predicts the reward of the env itself; with size_reward=True the step returns '
+                         "SizeReward's (make the env with size_reward=False)")
+    if not torch.is_tensor(actions):
+        actions = np.asarray(actions)
+        if actions.dtype.kind not in 'iu':
+            raise ValueError(f'peek: actions must be integers, got {actions.dtype}')
+    elif actions.is_floating_point() or actions.is_complex() or actions.dtype == torch.bool:
+        raise ValueError(f'peek: actions must be integers, got {actions.dtype}')
+    P.shape_of(actions, env.num_envs)
+    if not (torch.is_tensor(actions) and actions.dtype == torch.int32 and actions.device == env.device
+            and actions.is_contiguous()):
+        with torch.cuda.stream(alloc_stream):
+            # (anything outside 0..17 is a no-op whatever its width: it becomes -1 before the narrowing, which would wrap a
+            # wide value into the range)
+            if torch.is_tensor(actions):
+                host = torch.where((actions < 0) | (actions > 17), torch.full_like(actions, -1), actions)
+            else:
+                host = torch.from_numpy(np.where((actions < 0) | (actions > 17), -1, actions).astype(np.int32))
+            actions = host.to(device=env.device, dtype=torch.int32).contiguous()
+    env._in_use(actions)
+    root, sl, cfg = env._root(), env._sl, env.cfg
+    agent, grid, occ = env._rows
+    state = [grid, occ, root.hist_buf[sl], root.aux_buf[sl], agent, root.task_target, root.task_start, root.task_meta,
+             root.task_index]
+    return P.launch(state, env.num_envs, actions, (cfg.right_placement_scale, cfg.wrong_placement_scale, cfg.max_steps,
+                                                   cfg.select_and_place), gamma, names, out, env.device, stream,
+                    alloc_stream)
 
 
 def _check_gain(other_space, size_reward):
