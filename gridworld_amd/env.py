@@ -394,6 +394,16 @@ class GridWorld:
             raise ValueError(f'peek: actions must be [K, H], got shape {a.shape}')
         return {k: t[0].cpu().numpy() for k, t in self._vec.peek(a, gamma=gamma).items()}
 
+    def vox_obs(self, spec):
+        """The state of the last reset / step in the layout `spec` (a VoxSpec or a dict of its arguments;
+        VecGridWorld.vox_obs), as numpy [K * C, 9, S, S]: every slot holds the current planes
+        (the env keeps no stack between calls).  bfloat16, which numpy lacks, comes back as its float32 values."""
+        from .vox import VoxSpec
+        v, spec = self._vec, VoxSpec.of(spec)
+        goal = v.goal(want=True, todo=True) if spec.needs() else None
+        x = v.vox_obs(spec, goal=goal)[0]
+        return (x.float() if x.dtype is torch.bfloat16 else x).cpu().numpy()
+
     def render(self):
         """Renderer.render() (gridworld/render.py:129-144): the current frame as RGBA uint8 [H, W, 4], row 0 on top."""
         if not self._renders():

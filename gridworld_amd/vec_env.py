@@ -18,6 +18,7 @@ from . import goal as G
 from . import peek as P
 from . import query as Q
 from . import render as R
+from . import vox as X
 
 
 def _as_rows(x, device, n=None):
@@ -148,11 +149,11 @@ class _Rows:
         self._sl = sl
         self._rows = (root.agent_buf[sl], root.grid_buf[sl], root.occ_buf[sl])   # the state a frame is drawn from
 
-    def _follow_with(self, pov, mask, goal=None):
+    def _follow_with(self, pov, mask, goal=None, vox=None):
         """The persistent tensors that follow the state (a _Pov or None; obs['action_mask'] or None; the dict of the
-        goal query's outputs or None): this range's rows of them, and the observation dict that holds them beside the
-        state's views."""
-        self._pov, self._mask, self._goal = pov, mask, goal
+        goal query's outputs or None; the (VoxSpec, obs['vox_obs']) pair or None): this range's rows of them, and the
+        observation dict that holds them beside the state's views."""
+        self._pov, self._mask, self._goal, self._vox = pov, mask, goal, vox
         self.pov = pov.tensors.get('rgb') if pov else None
         self.pov_obs = pov.obs if pov else None
         self._obs = {'agentPos': self.agent_pos, 'inventory': self.inventory, 'compass': self.compass.unsqueeze(1),
@@ -165,6 +166,8 @@ class _Rows:
             self._obs.update(goal)
             if 'gain' in goal:
                 self._goal_scratch()   # (before the first launch that follows, which may be a captured one)
+        if vox is not None:
+            self._obs['vox_obs'] = vox[1]
 
     def __del__(self):
         ctx = getattr(self, 'ctx', None)
@@ -197,33 +200,46 @@ class _Rows:
     # ---- what follows a launch ----
     def _follow(self, restart=None, fill=False, draw=True):
         """The ONE path after a launch that moved this range's state: the draw (renderer='hip'), then the action mask
-        (action_mask=True), then the goal query (goal=...), on the range's stream.
-        `restart` / `fill` are the stack's restart rule of the draw
-        (pov_obs; ignored without): a uint8 tensor [n] of the rows to restart -- a step's _ended(), reset(mask)'s
-        mask -- or fill=True for every row (a full reset); the range's first draw after an undrawn move fills too.
+        (action_mask=True), then the goal query (goal=...), then the voxel observation (vox_obs=..., which may read the
+        goal's rows), on the range's stream.
+        `restart` / `fill` are the stacks' restart rule of the draw and of the voxel observation
+        (pov_obs, vox_obs; ignored without): a uint8 tensor [n] of the rows to restart -- a step's _ended(),
+        reset(mask)'s mask -- or fill=True for every row (a full reset); the range's first draw after an undrawn move
+        fills too (ONE flag for both stacks, taken once: they are written by the same calls).
         draw=False is the move that draws nothing (the fused rollouts, load_state_dict): it raises that flag."""
+        stacks = (self._pov is not None and self._pov.obs is not None) or self._vox is not None
         if not draw:
             self._root()._fill.raise_()
-        elif self._pov is not None:
-            if self._pov.obs is not None:
-                fill = self._root()._fill.take(self) or fill
+        elif stacks:
+            fill = self._root()._fill.take(self) or fill
+        if draw and self._pov is not None:
             self._draw(None, restart, fill)
         self._follow_mask()
         self._follow_goal()
+        if draw and self._vox is not None:
+            self._write_vox(None, restart, fill)
 
     def _follow_captured(self, stream, first, last):
         """_follow() after a step inside a captured chain, on the capture's stream (`first` / `last`: of the chain's
         steps).  A stack of K > 1 frames takes every step's frame, so the draw follows each step, the first with the
         captured form of the restart rule (_FillFlag.captured); otherwise one draw follows the last step's mask --
         what the eager loop's last step() leaves."""
-        pov = self._pov
-        if pov is not None and pov.stacked:
+        pov, vox = self._pov, self._vox
+        pov_stacked, vox_stacked = pov is not None and pov.stacked, vox is not None and vox[0].stack > 1
+        if pov_stacked or vox_stacked:   # (one captured mask for both stacks, as _follow takes the flag once)
             restart = self._ended()
-            self._draw(stream, self._root()._fill.captured(self._sl, restart) if first else restart)
+            if first:
+                restart = self._root()._fill.captured(self._sl, restart)
+        if pov_stacked:
+            self._draw(stream, restart)
         self._follow_mask(stream)
         self._follow_goal(stream)
         if last and pov is not None and not pov.stacked:
             self._draw(stream)
+        if vox_stacked:
+            self._write_vox(stream, restart)
+        elif last and vox is not None:
+            self._write_vox(stream)
 
     def _follow_mask(self, stream=None):
         if self._mask is not None:
@@ -267,6 +283,15 @@ class _Rows:
             _render_rows(self, pov.tensors['rgb'], 3, None, None, stream)
         else:
             _render_rows(self, pov.tensors, 3, None, tuple(pov.tensors), stream)
+
+    def _write_vox(self, stream=None, restart=None, fill=False):
+        """Writes obs['vox_obs'] from this range's state rows (and its rows of the goal's planes) on `stream` (a
+        capture's); without one on the range's own, where the tensor is then marked as in use."""
+        spec, data = self._vox
+        if stream is None:
+            stream = self._stream()
+            self._in_use(data)
+        _vox_rows(self, spec, data, restart, fill, self._goal, stream)
 
     def step_walking_ptr(self, actions_i32):
         """Hot-loop variant: `actions_i32` is already a contiguous int32 device tensor [n], launched on the range's
@@ -368,6 +393,25 @@ class _Rows:
         self._in_use(*res.values())
         return res
 
+    # ---- the state as the tensor a policy network reads (libigw_vox.so, include/igw_vox.h) ----
+    def vox_obs(self, spec, out=None, restart=None, fill=False, goal=None):
+        """Every env's CURRENT state in the layout `spec` (a vox.VoxSpec or a dict of its arguments; DESIGN.md section
+        14): a [N, K * C, 9, S, S] tensor of spec.dtype -- channel-first one-hot / occupancy planes of the grid, the
+        target and the goal query's rows, the agent's body, in the world's or the agent's frame, the last K calls
+        stacked.  One igw_vox_obs launch on the range's stream that shifts the new planes into `out` (the tensor an
+        earlier call returned), restarting the stack of env i where `restart` (a uint8 / bool device tensor [N], any
+        stride) is not 0, of every env with fill=True.  out=None returns a new, filled tensor; with `out` nothing is
+        allocated, so the call can be captured.  'want' / 'todo' planes are read from `goal`, the dict
+        goal(want=True, todo=True) returned (ValueError without it).  Every action space."""
+        spec = X.VoxSpec.of(spec)
+        if restart is not None and not (torch.is_tensor(restart) and restart.dtype in (torch.uint8, torch.bool)):
+            with torch.cuda.stream(self.stream):
+                restart = torch.as_tensor(restart, device=self.device).ne(0).to(torch.uint8)
+        self._in_use(out, restart, *(goal or {}).values())
+        res = _vox_rows(self, spec, out, restart, fill, goal, self._stream(), self.stream)
+        self._in_use(res)
+        return res
+
     # ---- first-person frames (libigw_render.so, include/igw_render.h) ----
     def render_pov(self, out=None, channels=3, size=None, outputs=None, codec=None, quality=90):
         """The first-person frame of every env's CURRENT state (see _make_views for auto-reset envs): uint8
@@ -399,7 +443,8 @@ class VecGridWorld(_Rows):
                  size_reward=True, max_steps=250, right_placement_scale=1., wrong_placement_scale=0.1,
                  discretize=True, autoreset=False, num_tasks=None, lanes_per_env=0, debug_flags=0, env_index_base=0,
                  host_records=False, render=False, render_size=(64, 64), target_in_obs=False, vector_state=True, name='', fake=False,
-                 renderer=None, pov_outputs=('rgb',), pov_obs=None, pov_frame=True, action_mask=False, goal=False):
+                 renderer=None, pov_outputs=('rgb',), pov_obs=None, pov_frame=True, action_mask=False, goal=False,
+                 vox_obs=None):
         """create_env's keyword arguments (gridworld/env.py:333-338) plus the batch's own: num_envs, device,
         autoreset (reset inside step), num_tasks (rows of the task table, default num_envs), lanes_per_env
         (0 = automatic), env_index_base (global index of env 0: rank / sub-batch offset), debug_flags (IGW_DIAG
@@ -429,7 +474,14 @@ class VecGridWorld(_Rows):
         igw_action_mask launch on the same stream after the step / reset launch (and after the draw).
         goal=True, or a tuple of 'want', 'todo', 'gain' (True = ('todo',)), adds obs['align'], obs['fit'] and the
         outputs named (gain: obs['gain'] and obs['ends']): persistent tensors of goal()'s layout, rewritten by one
-        igw_goal launch after the mask's.  'gain' has goal(gain=True)'s conditions."""
+        igw_goal launch after the mask's.  'gain' has goal(gain=True)'s conditions.
+        vox_obs (a vox.VoxSpec or a dict of its arguments) adds obs['vox_obs'], the state as the tensor a policy
+        network reads (vox_obs()): a persistent [N, K * C, 9, S, S] tensor of the spec's dtype,
+        rewritten by one igw_vox_obs launch after the goal's.  Its 'want' / 'todo' planes are the goal query's, so
+        `goal` has to name them.  The stack's episode boundaries are pov_obs's: reset() fills, reset(mask) the masked
+        envs, step() with autoreset=True the envs whose episode just ended, with autoreset=False none; after anything
+        that moves the state without following (rollout, rollout_actions, load_state_dict, set_tasks) the next write
+        fills."""
         if renderer not in (None, 'hip'):
             raise ValueError(f"unknown renderer {renderer!r}; the one renderer is 'hip'")
         pov_outputs = R.check_outputs(pov_outputs)
@@ -443,6 +495,12 @@ class VecGridWorld(_Rows):
             pov_obs = R.ObsSpec.of(pov_obs)
         elif not pov_frame:
             raise ValueError('pov_frame=False needs pov_obs (there would be nothing to draw)')
+        if vox_obs is not None:
+            vox_obs = X.VoxSpec.of(vox_obs)
+            held_names = ('todo',) if goal is True else tuple(goal or ())
+            lack = [k for k in vox_obs.needs() if k not in held_names]
+            if lack:
+                raise ValueError(f"vox_obs reads the goal query's {lack}: name them in goal= (goal={tuple(lack)!r})")
         if render and not fake and renderer is None:
             raise NotImplementedError("render=True needs renderer='hip' (the batched HIP ray caster of the "
                                       "first-person frame); or pass render=False")
@@ -529,7 +587,12 @@ class VecGridWorld(_Rows):
             held = G.outputs(N, ('align', 'fit') + tuple(k for k in ('want', 'todo') if k in goal) +
                              (('gain', 'ends') if 'gain' in goal else ()), dev)
         # obs['action_mask'] (action_mask=True): rewritten by every reset / step, and by whatever else moves the state
-        self._follow_with(pov, z((N, Q.ACTIONS), torch.uint8) if action_mask else None, held)
+        self.vox_obs_spec = vox_obs
+        vox = None
+        if vox_obs is not None:
+            X.load()
+            vox = (vox_obs, torch.zeros(vox_obs.shape(N), dtype=vox_obs.dtype, device=dev))
+        self._follow_with(pov, z((N, Q.ACTIONS), torch.uint8) if action_mask else None, held, vox)
 
     def _make_views(self):
         """The observation / result tensors of the env protocol (env.py:281-303) and the per-env task row / episode
@@ -842,13 +905,13 @@ class VecGridWorld(_Rows):
         """What _follow_captured reads and a capture may not allocate."""
         if self._pov is not None:
             self._atlas()
-            if self._pov.stacked:
-                self._fill.on_device(self)
+        if (self._pov is not None and self._pov.stacked) or (self._vox is not None and self._vox[0].stack > 1):
+            self._fill.on_device(self)
 
     def _replayed(self, chains):
         """What StepGraph.replay returns, step()'s result; the first draws of the graph's `chains` (its sub-batches, if
         it has any) took the stacks' fill flags."""
-        if self.pov_obs is not None:
+        if self.pov_obs is not None or self._vox is not None:
             self._fill.lowered(self, *chains)
         return self._obs.copy(), self.reward, self.done, {}
 
@@ -1059,7 +1122,8 @@ class SubBatch(_Rows):
         for k in self._VIEWS:
             setattr(self, k, getattr(parent, k)[sl])
         self._follow_with(parent._pov and parent._pov.rows(sl), None if parent._mask is None else parent._mask[sl],
-                          None if parent._goal is None else {k: t[sl] for k, t in parent._goal.items()})
+                          None if parent._goal is None else {k: t[sl] for k, t in parent._goal.items()},
+                          None if parent._vox is None else (parent._vox[0], parent._vox[1][sl]))
         if parent in parent._fill.drawn:   # (a sub-batch of a batch whose stacks are current starts with them)
             parent._fill.lowered(self)
         self._inherit_sampling()
@@ -1181,6 +1245,27 @@ def _peek_rows(env, actions, gamma, names, out, stream, alloc_stream=None):
     return P.launch(state, env.num_envs, actions, (cfg.right_placement_scale, cfg.wrong_placement_scale, cfg.max_steps,
                                                    cfg.select_and_place), gamma, names, out, env.device, stream,
                     alloc_stream)
+
+
+def _vox_rows(env, spec, out, restart, fill, goal, stream, alloc_stream=None):
+    """One igw_vox_obs launch (vox.launch) over the state rows of a whole VecGridWorld or of a SubBatch: 'grid' is the
+    range's grid rows, 'target' the task table's synthetic target plus its starting grid by task row, 'want' / 'todo'
+    the rows of `goal` (the dict goal() returned, or the range's persistent one)."""
+    lack = [k for k in spec.needs() if goal is None or k not in goal]
+    if lack:
+        raise ValueError(f"vox_obs: the planes {lack} are the goal query's: pass goal=env.goal(want=True, todo=True)")
+    root, sl, n = env._root(), env._sl, env.num_envs
+    agent, grid, _ = env._rows
+    sources = []
+    for name, _ in spec.planes:
+        if name == 'grid':
+            sources.append((grid.data_ptr(), None, L.GRID_STRIDE, 0))
+        elif name == 'target':
+            sources.append((root.task_target.data_ptr(), root.task_start.data_ptr(), L.GRID_STRIDE, 1))
+        else:
+            ptr, stride = X.rows_of(f'goal[{name!r}]', goal[name], n)
+            sources.append((ptr, None, stride, 0))
+    return X.launch(agent, root.aux_buf[sl], n, spec, sources, out, restart, fill, env.device, stream, alloc_stream)
 
 
 def _check_gain(other_space, size_reward):
