@@ -23,5 +23,6 @@ from . import aim  # noqa: F401,E402
 from .aim import aim_action, aim_decode  # noqa: F401,E402
 from . import peek  # noqa: F401,E402
 from .peek import peek_best, peek_decode  # noqa: F401,E402
+from . import peek_dict  # noqa: F401,E402
 from . import vox  # noqa: F401,E402
 from .vox import VoxSpec, vox_channel_names  # noqa: F401,E402

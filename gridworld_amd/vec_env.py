@@ -16,6 +16,7 @@ from . import aim as A
 from . import codec as K
 from . import goal as G
 from . import peek as P
+from . import peek_dict as PD
 from . import query as Q
 from . import render as R
 from . import vox as X
@@ -390,6 +391,29 @@ class _Rows:
         names = P.check_outputs(outputs)
         self._in_use(*(out or {}).values())
         res = _peek_rows(self, actions, gamma, names, out, self._stream(), self.stream)
+        self._in_use(*res.values())
+        return res
+
+    # ---- ... of the flying and the walking Dict spaces (libigw_peek_dict.so, include/igw_peek_dict.h) ----
+    def peek_dict(self, actions, gamma=1.0, outputs=PD.OUTPUTS, out=None):
+        """peek() for the flying and the walking Dict (discretize=False) action spaces: what every
+        env would be paid, when its episode would end, what it would build and where it would stand if it played each of
+        K sequences of H actions from its CURRENT state, which is not touched.  `actions`: a dict with the keys of the
+        env's own step() -- flying: movement [.., 3], camera [.., 2], inventory [..], placement [..]; walking Dict:
+        buttons [.., 8] (forward, back, left, right, jump, attack, use, hotbar), camera [.., 2] -- every entry behind
+        the same leading shape [K, H] (the same sequences for every env) or [N, K, H], 1 <= K <= 4096, 1 <= H <= 32;
+        an entry is converted to a contiguous device tensor of the step's dtype (float32, int32, uint8) only if it is
+        not one already.  An invalid component of an action (a value that is not finite, a camera delta beyond
+        +-1e6, an inventory / hotbar id outside 0..6, a placement outside 0..2) runs as the no-op the step makes of it;
+        nothing is counted.  Returns peek()'s dict of the `outputs` named (reward, ends, change, pose, ret; peek_decode
+        and peek_best read it).  One launch on the range's stream; `out`: a dict of tensors to write, as an earlier call
+        returned them; with every output given and the actions already such device tensors nothing is allocated, so
+        the call can be captured.  ValueError in the Discrete(18) space (that is env.peek), with size_reward=True,
+        for missing or extra keys, leading shapes that differ, K or H out of range, a wrong rank, a first dimension
+        that is not N, and for empty or unknown outputs."""
+        names = PD.check_outputs(outputs)
+        self._in_use(*(out or {}).values())
+        res = _peek_dict_rows(self, actions, gamma, names, out, self._stream(), self.stream)
         self._in_use(*res.values())
         return res
 
@@ -1245,6 +1269,28 @@ def _peek_rows(env, actions, gamma, names, out, stream, alloc_stream=None):
     return P.launch(state, env.num_envs, actions, (cfg.right_placement_scale, cfg.wrong_placement_scale, cfg.max_steps,
                                                    cfg.select_and_place), gamma, names, out, env.device, stream,
                     alloc_stream)
+
+
+def _peek_dict_rows(env, actions, gamma, names, out, stream, alloc_stream=None):
+    """One igw_peek_flying / igw_peek_walking_dict launch (peek_dict.launch) over the state rows of a whole VecGridWorld
+    or of a SubBatch."""
+    if not (env.flying or env.walk_dict):
+        raise ValueError('peek_dict is defined for the flying and the walking Dict action spaces; in the Discrete(18) '
+                         'space call env.peek')
+    if env.cfg.size_reward:
+        raise ValueError('peek_dict predicts the reward of the env itself; with size_reward=True the step returns '
+                         "SizeReward's (make the env with size_reward=False)")
+    space = 'flying' if env.flying else 'walking_dict'
+    PD.shape_of(space, actions, env.num_envs)
+    root, sl, cfg = env._root(), env._sl, env.cfg
+    agent, grid, occ = env._rows
+    state = [grid, occ, root.hist_buf[sl], root.aux_buf[sl], agent, root.task_target, root.task_start, root.task_meta,
+             root.task_index]
+    res, bufs = PD.launch(space, state, env.num_envs, actions, (cfg.right_placement_scale, cfg.wrong_placement_scale,
+                                                                cfg.max_steps, cfg.select_and_place), gamma, names, out,
+                          env.device, stream, alloc_stream)
+    env._in_use(*bufs)
+    return res
 
 
 def _vox_rows(env, spec, out, restart, fill, goal, stream, alloc_stream=None):
