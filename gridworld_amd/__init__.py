@@ -26,3 +26,5 @@ from .peek import peek_best, peek_decode  # noqa: F401,E402
 from . import peek_dict  # noqa: F401,E402
 from . import vox  # noqa: F401,E402
 from .vox import VoxSpec, vox_channel_names  # noqa: F401,E402
+from . import worth  # noqa: F401,E402
+from .worth import worth_decode, worth_plane_names  # noqa: F401,E402

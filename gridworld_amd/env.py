@@ -384,6 +384,21 @@ class GridWorld:
             out['ends'] = out['ends'].astype(np.bool_)
         return out
 
+    def worth(self, allow=None, stocked=False):
+        """What this env would pay for every single-cell edit of the state of the last reset / step (VecGridWorld.worth,
+        DESIGN.md section 16), as numpy: word int16 [7, 9, 11, 11] (worth_decode reads it) and best int32 [4] = (plane,
+        cell, word, candidates).  `allow`: None or a uint8 / bool array [2, 9, 11, 11] (breaks, places) that gates
+        `best`; stocked=True leaves the colours with an empty inventory out of it.  Every action space."""
+        v = self._vec
+        if allow is not None:
+            a = np.asarray(allow)
+            if a.shape != (2, 9, 11, 11) or a.dtype.kind not in 'biu':
+                raise ValueError(f'worth: allow must be a bool / integer array [2, 9, 11, 11], got {a.dtype} {a.shape}')
+            rows = torch.zeros((1, 2, 1104), dtype=torch.uint8)
+            rows[0, :, :1089] = torch.from_numpy((a != 0).astype(np.uint8).reshape(2, 1089))
+            allow = rows.to(v.device)
+        return {k: t[0].cpu().numpy() for k, t in v.worth(allow=allow, stocked=stocked).items()}
+
     def peek(self, actions, gamma=1.0):
         """What this env would be paid, when it would end, what it would build and where it would stand if it played
         each of the K sequences of H actions `actions` (integers [K, H]) from the state of the last reset / step

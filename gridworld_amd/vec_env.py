@@ -20,6 +20,7 @@ from . import peek_dict as PD
 from . import query as Q
 from . import render as R
 from . import vox as X
+from . import worth as W
 
 
 def _as_rows(x, device, n=None):
@@ -414,6 +415,28 @@ class _Rows:
         names = PD.check_outputs(outputs)
         self._in_use(*(out or {}).values())
         res = _peek_dict_rows(self, actions, gamma, names, out, self._stream(), self.stream)
+        self._in_use(*res.values())
+        return res
+
+    # ---- what every single-cell edit would be paid (libigw_worth.so, include/igw_worth.h) ----
+    def worth(self, outputs=W.OUTPUTS, allow=None, stocked=False, out=None):
+        """What the env would pay for every single-cell edit of every env's CURRENT state, which is not touched (DESIGN.md
+        section 16): a dict of the `outputs` named,
+          word int16 [N, 7, 9, 11, 11]   plane 0: break the cell, planes 1..6: place that colour in it (worth_plane_names);
+                                         right | (wrong + 1) << 12 | ends << 14, -1 where the edit is invalid (a break of
+                                         an empty cell, a place into a full one); worth_decode reads it
+          best int32 [N, 4]              (plane, cell, word, candidates) of the best-paid edit, (-1, -1, -1, 0) without one
+        `word` is a strided view of seven 1104-word rows per env, each in the layout of `grid`.  `best` is chosen among
+        the valid edits that pass two gates, neither of which changes `word`: `allow`, a uint8 device tensor [N, 2, 9,
+        11, 11] with 1104-byte rows (worth.allow_from_aim builds it from aim()'s planes) or contiguous [N, 2, 1104] --
+        plane 0 gates the breaks of a cell, plane 1 the places into it -- and stocked=True, which leaves out the colours
+        whose inventory is empty.  Inventory, adjacency, the agent's overlap and reach do not gate validity.  One
+        igw_worth launch on the range's stream; `out`: a dict of tensors to write, as an earlier call returned them;
+        with every output given nothing is allocated, so the call can be captured.  Every action space; SizeReward's
+        reward is not predicted.  ValueError for empty or unknown outputs, a wrong `out` and a wrong `allow`."""
+        names = W.check_outputs(outputs)
+        self._in_use(allow, *(out or {}).values())
+        res = _worth_rows(self, names, allow, stocked, out, self._stream(), self.stream)
         self._in_use(*res.values())
         return res
 
@@ -1312,6 +1335,16 @@ def _vox_rows(env, spec, out, restart, fill, goal, stream, alloc_stream=None):
             ptr, stride = X.rows_of(f'goal[{name!r}]', goal[name], n)
             sources.append((ptr, None, stride, 0))
     return X.launch(agent, root.aux_buf[sl], n, spec, sources, out, restart, fill, env.device, stream, alloc_stream)
+
+
+def _worth_rows(env, names, allow, stocked, out, stream, alloc_stream=None):
+    """One igw_worth launch (worth.launch) over the state rows of a whole VecGridWorld or of a SubBatch."""
+    root, sl, cfg = env._root(), env._sl, env.cfg
+    agent, _, _ = env._rows
+    state = [root.grid_buf[sl], root.hist_buf[sl], root.aux_buf[sl], agent, root.task_target, root.task_start,
+             root.task_meta, root.task_index]
+    return W.launch(state, env.num_envs, (cfg.right_placement_scale, cfg.wrong_placement_scale, cfg.max_steps), allow,
+                    stocked, names, out, env.device, stream, alloc_stream)
 
 
 def _check_gain(other_space, size_reward):
