@@ -28,3 +28,5 @@ from . import vox  # noqa: F401,E402
 from .vox import VoxSpec, vox_channel_names  # noqa: F401,E402
 from . import worth  # noqa: F401,E402
 from .worth import worth_decode, worth_plane_names  # noqa: F401,E402
+from . import relabel  # noqa: F401,E402  (the module is callable: G.relabel(...) is relabel.relabel(...))
+from .relabel import relabel_future  # noqa: F401,E402

@@ -1,7 +1,7 @@
 """Builds gridworld_amd/libigw_hip.so (HIP kernels + C ABI) for gfx950 with hipcc.
 
     python -m gridworld_amd.build            # build if stale: the step library, then the render, codec, query, goal,
-    python -m gridworld_amd.build --force    # aim, peek, peek_dict, vox and worth libraries (each module's own build())
+    python -m gridworld_amd.build --force    # aim, peek, peek_dict, vox, worth and relabel libraries (each module's own build())
 
 hipcc cross-compiles without a GPU.  -ffp-contract=off is REQUIRED: the reference computes
 in IEEE binary64 with one rounding per operation; never add fast-math flags.
@@ -181,6 +181,6 @@ def build(force=False, extra_flags=(), verbose=False, diag=False):
 if __name__ == '__main__':
     print(build(force='--force' in sys.argv, verbose=True, diag='--diag' in sys.argv))
     if '--diag' not in sys.argv:   # ... and the libraries beside the step library, each by its own module's build()
-        from . import aim, codec, goal, peek, peek_dict, query, render, vox, worth
-        for module in (render, codec, query, goal, aim, peek, peek_dict, vox, worth):
+        from . import aim, codec, goal, peek, peek_dict, query, relabel, render, vox, worth
+        for module in (render, codec, query, goal, aim, peek, peek_dict, vox, worth, relabel):
             print(module.build(force='--force' in sys.argv))

@@ -399,6 +399,16 @@ class GridWorld:
             allow = rows.to(v.device)
         return {k: t[0].cpu().numpy() for k, t in v.worth(allow=allow, stocked=stocked).items()}
 
+    def relabel(self, goals='final', gamma=1.0, outputs=('reward', 'done', 'end', 'ret')):
+        """What this env's most recent finished episode would have been paid under other targets (VecGridWorld.relabel,
+        DESIGN.md section 17), as numpy: the outputs named with the env's row taken ([G, L] per step, [G] per goal),
+        plus length and valid.  `goals`: 'final', 'own', entries [G] or targets [G, 9, 11, 11].  Needs the episode log
+        (the Logged wrapper, or enable_trajectory_log on the batch)."""
+        v = self._vec
+        if not isinstance(goals, str):
+            goals = torch.as_tensor(np.asarray(goals))[None].to(v.device)
+        return {k: t[0].cpu().numpy() for k, t in v.relabel(goals, gamma=gamma, outputs=outputs).items()}
+
     def peek(self, actions, gamma=1.0):
         """What this env would be paid, when it would end, what it would build and where it would stand if it played
         each of the K sequences of H actions `actions` (integers [K, H]) from the state of the last reset / step

@@ -18,6 +18,7 @@ from . import goal as G
 from . import peek as P
 from . import peek_dict as PD
 from . import query as Q
+from . import relabel as RL
 from . import render as R
 from . import vox as X
 from . import worth as W
@@ -437,6 +438,32 @@ class _Rows:
         names = W.check_outputs(outputs)
         self._in_use(allow, *(out or {}).values())
         res = _worth_rows(self, names, allow, stocked, out, self._stream(), self.stream)
+        self._in_use(*res.values())
+        return res
+
+    # ---- rewards of logged episodes under other targets (libigw_relabel.so, include/igw_relabel.h) ----
+    def relabel(self, goals='final', gamma=1.0, outputs=RL.DEFAULT, out=None):
+        """Hindsight relabelling of the episode log (enable_trajectory_log / EpisodeLogger): for
+        every logged env of this range, E of them, the reward, done and return its most recent FINISHED episode would
+        have had under each of G other targets.  `goals`: 'final' (the grid the episode ended with), 'own' (the episode's
+        own target, task_target + task_start of its task row: it reproduces the logged rewards), an integer tensor
+        [E, G] of entries of the episode itself (0 = its start, its length = its final grid; relabel_future draws HER's
+        "future" entries), or a tensor of targets [E, G, 9, 11, 11] / [E, G, 1104].  A dict of the `outputs` named --
+          reward float32 / done uint8 / progress int16 [E, G, L]   per step, +0 past the episode's length (L = the log's
+                                                                    capacity; progress is the cached max_int)
+          end int32 [E, G], ret float32 [E, G]                      the first done step (0: none) and the return
+                                                                    discounted by `gamma` up to it
+          target_size int16 [E, G], target int8 [E, G, 9, 11, 11]   the goals used (vox_obs / render_views read them)
+        -- plus length int32 [E] and valid uint8 [E]: 0 for an env without a finished episode, whose rows are padding.
+        Slots, lengths and starting rows come from the log's heads and the task table with torch operations on the
+        range's stream and the kernel reads only the records' change words: no env state is touched and the host never
+        waits, so the call can be captured.  It uses the env's scales and max_steps, every action space; like the log's
+        grids it reads the episode's task row, so a set_tasks (or the RandomTasks generator) that rewrote the row since
+        changes the start.  ValueError without a log, for a range that holds no logged env, with size_reward=True, and
+        for empty or unknown outputs or a wrong `out`."""
+        names = RL.check_outputs(outputs)
+        self._in_use(*(out or {}).values())
+        res = _relabel_rows(self, goals, gamma, names, out, self._stream(), self.stream)
         self._in_use(*res.values())
         return res
 
@@ -1345,6 +1372,66 @@ def _worth_rows(env, names, allow, stocked, out, stream, alloc_stream=None):
              root.task_meta, root.task_index]
     return W.launch(state, env.num_envs, (cfg.right_placement_scale, cfg.wrong_placement_scale, cfg.max_steps), allow,
                     stocked, names, out, env.device, stream, alloc_stream)
+
+
+def finished_episodes(heads, lo, cap):
+    """(first int64 [n], length int32 [n], task int64 [n], valid uint8 [n]) of the most recent finished episode of every
+    env of a slice heads[lo:lo + n] of the log's heads (include/igw.h: task row, steps recorded, episode number,
+    finished per slot): plain torch on the heads' device, nothing comes to the host."""
+    n = heads.shape[0]
+    fin = (heads[:, :, 3] != 0) & (heads[:, :, 1] > 0)
+    number = heads[:, :, 2].long() & 0xffffffff
+    score = torch.where(fin, number, torch.full_like(number, -1))
+    slot = score.argmax(1)
+    valid = score.gather(1, slot[:, None])[:, 0] >= 0
+    row = heads.gather(1, slot[:, None, None].expand(n, 1, 4))[:, 0]
+    length = torch.where(valid, row[:, 1].clamp(0, cap), torch.zeros_like(row[:, 1]))
+    task = torch.where(valid, row[:, 0], torch.zeros_like(row[:, 0])).long()
+    first = ((torch.arange(n, device=heads.device) + lo) * 2 + slot) * cap
+    return first, length.to(torch.int32), task, valid.to(torch.uint8)
+
+
+def _relabel_rows(env, goals, gamma, names, out, stream, alloc_stream=None):
+    """One igw_relabel launch (relabel.launch) over the logged envs of a whole VecGridWorld or of a SubBatch."""
+    root, cfg, dev = env._root(), env.cfg, env.device
+    if cfg.size_reward:
+        raise ValueError('relabel predicts the reward of the env itself; with size_reward=True the step returns '
+                         "SizeReward's (make the env with size_reward=False)")
+    if root._traj is None:
+        raise ValueError('relabel reads the episode log: call enable_trajectory_log() or make an EpisodeLogger first')
+    rec, heads, n_logged, cap = root._traj
+    lo, hi = env.lo, min(env.lo + env.num_envs, n_logged)
+    if hi <= lo:
+        raise ValueError(f'relabel: none of the envs [{env.lo}, {env.lo + env.num_envs}) is logged (the log holds the first {n_logged})')
+    e = hi - lo
+    with torch.cuda.stream(alloc_stream):
+        first, length, task, valid = finished_episodes(heads[lo:hi], lo, cap)
+        task = task.clamp(0, root.num_tasks - 1)
+        starts = root.task_start.index_select(0, task)
+        targets = at = None
+        if isinstance(goals, str):
+            if goals == 'final':
+                at = length[:, None].contiguous()
+            elif goals == 'own':
+                targets = (root.task_target.index_select(0, task) + starts)[:, None, :].contiguous()
+            else:
+                raise ValueError(f"relabel: goals is 'final', 'own', entries [E, G] or targets [E, G, 9, 11, 11], got {goals!r}")
+        else:
+            g = goals if torch.is_tensor(goals) else torch.as_tensor(np.asarray(goals))
+            if g.is_floating_point() or g.is_complex() or g.dtype == torch.bool:
+                raise ValueError(f'relabel: goals must be integers, got {g.dtype}')
+            if g.dim() == 2 and g.shape[0] == e:
+                at = g.to(device=dev, dtype=torch.int32).contiguous()
+            elif g.dim() in (3, 5) and g.shape[0] == e:
+                targets = RL.grid_rows(g, dev, (e, int(g.shape[1])))
+            else:
+                raise ValueError(f'relabel: goals must be entries [{e}, G] or targets [{e}, G, 9, 11, 11] / [{e}, G, 1104], '
+                                 f'got shape {tuple(g.shape)}')
+    env._in_use(first, length, starts, targets, at, valid)
+    res = RL.launch(rec, first, length, starts, targets, at, cap, (cfg.right_placement_scale, cfg.wrong_placement_scale,
+                                                                   cfg.max_steps), gamma, names, out, dev, stream, alloc_stream)
+    res.update(length=length, valid=valid)
+    return res
 
 
 def _check_gain(other_space, size_reward):

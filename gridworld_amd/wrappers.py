@@ -7,6 +7,7 @@ import torch
 
 from . import _lib as L
 from . import codec as K
+from . import relabel as RL
 from . import render as R
 from . import spaces
 from .env import Wrapper  # noqa: F401  (gridworld/env.py:306-314; re-exported: the reference imports gym.Wrapper here)
@@ -156,6 +157,55 @@ class EpisodeLogger:
             jpegs = K.jpeg_bytes(*K.encode_jpeg(torch.from_numpy(np.ascontiguousarray(episode['pov']))
                                                 .to(self.vec.device), self.pov_quality))
         return K.write_avi(path, jpegs, self.vec.render_size, fps)
+
+    def relabel(self, episodes=None, goals='final', gamma=1.0, outputs=RL.DEFAULT):
+        """Hindsight rewards of collected episodes (VecGridWorld.relabel): one igw_relabel launch for
+        `episodes` (dicts collect() returned; default: all of them) under G goals each.  `goals`: 'final' (the grid the
+        episode ended with), 'own' (its task row's target as the task table holds it now), integer entries [G] or [E, G]
+        of the episode itself, or targets [E, G, 9, 11, 11].  The change words are rebuilt from each dict's `grid`
+        sequence, so an episode whose slot of the device log was overwritten since still answers.  Every dict gains
+        `<output>_relabel` for the outputs named -- reward, done, progress as [G, T] (T the episode's steps), end, ret,
+        target_size as [G], target as [G, 9, 11, 11] -- and the list is returned."""
+        v = self.vec
+        eps = list(self.episodes if episodes is None else episodes)
+        names = RL.check_outputs(outputs)
+        if v.cfg.size_reward:
+            raise ValueError('relabel predicts the reward of the env itself; with size_reward=True the step returns '
+                             "SizeReward's (make the env with size_reward=False)")
+        if not eps:
+            return eps
+        dev = v.device
+        length = np.array([len(ep['reward']) for ep in eps], np.int64)
+        first = np.concatenate([[0], np.cumsum(length)])
+        rec = np.zeros((max(int(first[-1]), 1), L.TRAJ_BYTES), np.uint8)
+        for i, ep in enumerate(eps):
+            g = np.asarray(ep['grid']).reshape(len(ep['grid']), -1)
+            diff = g[1:] != g[:-1]
+            cell = diff.argmax(1)
+            word = np.where(diff.any(1), cell | g[1:][np.arange(len(cell)), cell].astype(np.int64) << 11, 0xffff)
+            rec[first[i]:first[i + 1], 40:42] = word.astype(np.uint16).view(np.uint8).reshape(-1, 2)
+        starts = np.stack([np.asarray(ep['grid'][0]).reshape(-1) for ep in eps]).astype(np.int8)
+        kw = {}
+        if isinstance(goals, str) and goals == 'final':
+            kw['at'] = length[:, None]
+        elif isinstance(goals, str) and goals == 'own':
+            rows = torch.as_tensor([ep['task'] for ep in eps], device=dev)
+            kw['targets'] = (v.task_target.index_select(0, rows) + v.task_start.index_select(0, rows))[:, None, :]
+        elif isinstance(goals, str):
+            raise ValueError(f"relabel: goals is 'final', 'own', entries or targets, got {goals!r}")
+        else:
+            g = np.asarray(goals.cpu() if torch.is_tensor(goals) else goals)
+            if g.ndim == 1:
+                g = np.broadcast_to(g, (len(eps), len(g)))
+            kw['at' if g.ndim == 2 else 'targets'] = np.ascontiguousarray(g)
+        res = RL.relabel(torch.from_numpy(rec).to(dev), first[:-1], length, starts, right_scale=v.cfg.right_placement_scale,
+                         wrong_scale=v.cfg.wrong_placement_scale, max_steps=v.cfg.max_steps, gamma=gamma, outputs=names,
+                         pad=max(int(length.max()), 1), **kw)
+        host = {k: t.cpu().numpy() for k, t in res.items()}
+        for i, ep in enumerate(eps):
+            for k, h in host.items():
+                ep[k + '_relabel'] = h[i, :, :length[i]] if k in ('reward', 'done', 'progress') else h[i]
+        return eps
 
     def collect(self, dump=True):
         """Decodes (and with dump=True writes) every logged episode that finished since the last call."""
