@@ -30,3 +30,4 @@ from . import worth  # noqa: F401,E402
 from .worth import worth_decode, worth_plane_names  # noqa: F401,E402
 from . import relabel  # noqa: F401,E402  (the module is callable: G.relabel(...) is relabel.relabel(...))
 from .relabel import relabel_future  # noqa: F401,E402
+from . import recall  # noqa: F401,E402  (the module is callable: G.recall(...) is recall.recall(...))

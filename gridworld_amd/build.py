@@ -184,3 +184,5 @@ if __name__ == '__main__':
         from . import aim, codec, goal, peek, peek_dict, query, relabel, render, vox, worth
         for module in (render, codec, query, goal, aim, peek, peek_dict, vox, worth, relabel):
             print(module.build(force='--force' in sys.argv))
+        from . import recall   # ... and the recall query's
+        print(recall.build(force='--force' in sys.argv))

@@ -18,6 +18,7 @@ from . import goal as G
 from . import peek as P
 from . import peek_dict as PD
 from . import query as Q
+from . import recall as RCL
 from . import relabel as RL
 from . import render as R
 from . import vox as X
@@ -464,6 +465,34 @@ class _Rows:
         names = RL.check_outputs(outputs)
         self._in_use(*(out or {}).values())
         res = _relabel_rows(self, goals, gamma, names, out, self._stream(), self.stream)
+        self._in_use(*res.values())
+        return res
+
+    # ---- voxel observations of logged transitions (libigw_recall.so, include/igw_recall.h) ----
+    def recall(self, spec, batch=None, seed=0, episode=None, step=None, goals=None, goal=None, outputs=RCL.ENV_DEFAULT,
+               out=None):
+        """A minibatch of logged transitions in the layout `spec` (a vox.VoxSpec or a dict of its arguments with the
+        planes 'grid' and 'target'): for B samples (e, t) -- step t of the most recent FINISHED
+        episode of the e-th logged env of this range -- obs and next_obs [B, K * C, 9, S, S], what a vox_obs stack of K
+        showed before and after the step, rebuilt from the log's change words and float32 poses by one igw_recall launch
+        on the range's stream.  Samples: `episode` and `step` ([B] integers, 1 <= step <= length), or `batch` of them
+        drawn with a torch generator seeded by `seed` (the env uniform, the step uniform over its episode).  A 'target'
+        plane shows the sample's goal: goals='own' (task_target + task_start of the episode's task row) or goals=r, the
+        dict relabel() returned with 'target', and `goal` [B], the column g of each sample (default 0); with r's 'reward'
+        / 'done' the result also holds reward_relabel / done_relabel [B], r's values at (e, g, t - 1).  A dict of the
+        `outputs` named -- obs, next_obs, record uint8 [B, 64] with recall.decode()'s views of it (action, reward, done,
+        inventory, agent_pos), valid uint8 [B] -- plus episode and step int32 [B].  A sample out of range, or of an env
+        without a finished episode, is padding: valid 0, its observations all `bias`, its record zeros.  Starts and reset
+        poses come from the task table by the head's task row with torch operations on the range's stream: no env state is
+        touched and the host never waits, so the call can be captured (with `episode` / `step` given: a torch generator
+        does not draw inside a capture); `out`: a dict of tensors to write, as an earlier call returned them.  Every
+        action space.  The poses are the LOG's (float32): next to a half-integer coordinate the
+        head cell can differ from the one the live vox_obs showed.  ValueError without a log, for a range that holds no
+        logged env, for 'want' / 'todo' planes, a 'target' plane without goals, and a wrong `out`."""
+        spec, _ = RCL.spec_of(spec)
+        names = RCL.check_outputs(outputs)
+        self._in_use(*(out or {}).values())
+        res = _recall_rows(self, spec, batch, seed, episode, step, goals, goal, names, out, self._stream(), self.stream)
         self._in_use(*res.values())
         return res
 
@@ -1431,6 +1460,77 @@ def _relabel_rows(env, goals, gamma, names, out, stream, alloc_stream=None):
     res = RL.launch(rec, first, length, starts, targets, at, cap, (cfg.right_placement_scale, cfg.wrong_placement_scale,
                                                                    cfg.max_steps), gamma, names, out, dev, stream, alloc_stream)
     res.update(length=length, valid=valid)
+    return res
+
+
+def _recall_rows(env, spec, batch, seed, episode, step, goals, goal, names, out, stream, alloc_stream=None):
+    """One igw_recall launch (recall.launch) over the logged envs of a whole VecGridWorld or of a SubBatch."""
+    root, dev = env._root(), env.device
+    if root._traj is None:
+        raise ValueError('recall reads the episode log: call enable_trajectory_log() or make an EpisodeLogger first')
+    rec, heads, n_logged, cap = root._traj
+    lo, hi = env.lo, min(env.lo + env.num_envs, n_logged)
+    if hi <= lo:
+        raise ValueError(f'recall: none of the envs [{env.lo}, {env.lo + env.num_envs}) is logged (the log holds the first {n_logged})')
+    e = hi - lo
+    if (episode is None) != (step is None):
+        raise ValueError('recall: give episode and step together, or batch= alone')
+    if episode is None and (batch is None or isinstance(batch, bool) or int(batch) != batch or int(batch) < 0):
+        raise ValueError(f'recall: give batch=, the number of samples to draw, or episode= and step=, got batch={batch!r}')
+
+    def ints(name, x, dtype):
+        t = x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))
+        if t.is_floating_point() or t.is_complex() or t.dtype == torch.bool or t.dim() != 1:
+            raise ValueError(f'recall: {name} must be integers [B], got {t.dtype} {tuple(t.shape)}')
+        return t.to(device=dev, dtype=dtype).contiguous()
+    if goals is not None and not (isinstance(goals, dict) and 'target' in goals) and not (isinstance(goals, str) and goals == 'own'):
+        raise ValueError("recall: goals is None, 'own' or the dict relabel() returned with 'target', got "
+                         f'{goals if isinstance(goals, str) else type(goals).__name__!r}')
+    if goals is None and RCL.needs_goal(spec):
+        raise ValueError("recall: a 'target' plane shows the sample's goal: pass goals='own' or goals=env.relabel(..., "
+                         "outputs=(..., 'target'))")
+    if goal is not None and not isinstance(goals, dict):
+        raise ValueError('recall: goal= names a column of goals=r, the dict relabel() returned')
+    with torch.cuda.stream(alloc_stream):
+        first, length, task, _ = finished_episodes(heads[lo:hi], lo, cap)
+        task = task.clamp(0, root.num_tasks - 1)
+        starts = root.task_start.index_select(0, task)
+        init_pose = root.task_meta.index_select(0, task)[:, :40].contiguous().view(torch.float64)   # x, y, z, yaw, pitch
+        if episode is None:
+            episode, step = RCL.sample(length, int(batch), seed)
+        else:
+            episode, step = ints('episode', episode, torch.int32), ints('step', step, torch.int32)
+            if episode.shape != step.shape:
+                raise ValueError(f'recall: episode and step must have one length, got {tuple(episode.shape)}, {tuple(step.shape)}')
+        b = episode.shape[0]
+        rows, index, extra = None, None, {}
+        if isinstance(goals, str):
+            rows = root.task_target.index_select(0, task) + starts
+        elif isinstance(goals, dict):
+            rows = goals['target']
+            if not torch.is_tensor(rows) or rows.dim() != 5 or rows.shape[0] != e or rows.device != dev:
+                raise ValueError(f"recall: goals['target'] must be relabel()'s [{e}, G, 9, 11, 11] on {dev}")
+            n_g = int(rows.shape[1])
+            g = torch.zeros_like(episode, dtype=torch.int64) if goal is None else ints('goal', goal, torch.int64)
+            if g.shape != episode.shape:
+                raise ValueError(f'recall: goal must be [{b}], got {tuple(g.shape)}')
+            ep = episode.long()
+            inside = (ep >= 0) & (ep < e) & (g >= 0) & (g < n_g)
+            index = torch.where(inside, ep * n_g + g, torch.full_like(g, -1))
+            for k in ('reward', 'done'):
+                if k in goals:
+                    t = goals[k]
+                    if not torch.is_tensor(t) or t.dim() != 3 or tuple(t.shape[:2]) != (e, n_g) or t.device != dev:
+                        raise ValueError(f"recall: goals[{k!r}] must be relabel()'s [{e}, {n_g}, L] on {dev}")
+                    at = (step.long() - 1)
+                    ok = inside & (at >= 0) & (at < length.index_select(0, ep.clamp(0, e - 1)).clamp(max=t.shape[2]))
+                    got = t[ep.clamp(0, e - 1), g.clamp(0, n_g - 1), at.clamp(0, t.shape[2] - 1)]
+                    extra[k + '_relabel'] = torch.where(ok, got, torch.zeros_like(got))
+    env._in_use(first, length, starts, init_pose, episode, step, rows, index)
+    space = 'flying' if env.flying else 'walking_dict' if env.walk_dict else 'walking'
+    res = RCL.launch(rec, first, length, starts, init_pose, episode, step, spec, rows, index, cap, names, out, dev, stream,
+                     alloc_stream, space)
+    res.update(extra, episode=episode, step=step)
     return res
 
 
