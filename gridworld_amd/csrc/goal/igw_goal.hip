@@ -10,12 +10,13 @@
 //     start) chunk it loaded as one dwordx4; both rows leave as dwordx4 stores.
 //   gain / ends: the row is parked in LDS once.  Per acting action the wavefront takes the changed cell's level block of
 //     the colour index (160 B), votes the cell's old colour out and its new colour in with LDS atomics -- sixteen target
-//     cells x four rotations per pass, the arithmetic of the step's histogram update restated below -- takes the
-//     maximum, and writes the row back from the registers that still hold it: one LDS copy, no undo pass.
+//     cells x four rotations per pass, the arithmetic of the step's histogram update on the level block staged here --
+//     takes the maximum, and writes the row back from the registers that still hold it: one LDS copy, no undo pass.
+// The colour index's layout, class1 and row_piece_max are igw_vote.h's, the query libraries' one copy.
 // Nothing synchronises across wavefronts: a wavefront without an env returns at once.
 #include <stdio.h>
 
-#include "../igw_device.h"
+#include "../igw_vote.h"
 #include "../../../include/igw_goal.h"
 
 namespace {
@@ -23,11 +24,6 @@ namespace {
 using namespace igw;
 
 constexpr int kActions = IGW_GOAL_ACTIONS;
-constexpr int kLvlBytes = IGW_LEVEL_INDEX_BYTES;   // one level block of a task's colour index (include/igw.h)
-constexpr int kLvlOffs = 16;                       // offs[15] behind the four rotation bounding boxes
-constexpr int kLvlCells = 32;                      // cells[<= 121]: (x + 5) << 4 | (z + 5), sorted by colour class
-static_assert(kLvlCells + LEVEL <= kLvlBytes && kLvlBytes % 16 == 0, "level index block layout");
-static_assert(HIST_ROW * 2 == WAVE * 16, "a wavefront holds a histogram row as one dwordx4 per lane");
 static_assert(CHUNKS > WAVE && CHUNKS <= 2 * WAVE, "a lane owns at most two chunks of a grid row");
 
 struct GoalParams {
@@ -56,21 +52,6 @@ struct WaveShared {
     alignas(16) uint8_t lvl[kLvlBytes];
     alignas(16) int8_t tgt[STRIDE];
 };
-
-// class + 1 of a synthetic colour in the colour index (0: nothing in a target can match it); a colour outside -7..7
-// clamps to the empty slice behind the last class (include/igw.h)
-__device__ inline int class1(int c) {
-    const int k = min(max(c + 7 + (int)((uint32_t)c >> 31), 0), 15);
-    return c == 0 ? 0 : k;
-}
-
-typedef unsigned short us2 __attribute__((ext_vector_type(2)));
-__device__ inline int row_piece_max(const uint4& v) {
-    const us2 m = __builtin_elementwise_max(
-        __builtin_elementwise_max(__builtin_bit_cast(us2, v.x), __builtin_bit_cast(us2, v.y)),
-        __builtin_elementwise_max(__builtin_bit_cast(us2, v.z), __builtin_bit_cast(us2, v.w)));
-    return (int)max((uint32_t)m.x, (uint32_t)m.y);
-}
 
 // the 16 bytes of chunk c of the `want` row: cell i = 16 c + j reads rotation `rot` of the LDS target at (x + dx, z + dz)
 __device__ inline uint4 want_chunk(const int8_t* tgt_s, int c, int dx, int dz, int rot) {

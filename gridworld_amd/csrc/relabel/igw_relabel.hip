@@ -10,7 +10,8 @@
 //   A goal given as an entry (`at`) is rebuilt first: the block walks the change words once, every wavefront applying
 //   the ones below its own entry to its copy of the starting row.
 //   The scoring walks the CHANGES, not the steps: of every 64 records (a lane each) a ballot keeps the ones that changed
-//   a cell; per change the wavefront votes with LDS atomics (the step's histogram update: the target cells of the
+//   a cell; per change the wavefront votes with LDS atomics (vote_change of igw_vote.h, the query libraries' one copy of
+//   the step's histogram update: the target cells of the
 //   cell's level and old colour lose a vote per rotation and admissible translation, those of the new colour gain one)
 //   and retakes the row maximum only when the block count of grid - start moved (a packed 16-bit maximum per lane and a
 //   DPP reduction); a cell recoloured in place votes but leaves the cached maximum as it is, as the step does.  The lanes
@@ -21,7 +22,7 @@
 // Vector stores only.  Every loop is bounded by L, by the 64 lanes of a ballot or by the 121 cells of a level.
 #include <stdio.h>
 
-#include "../igw_device.h"
+#include "../igw_vote.h"
 #include "../../../include/igw_relabel.h"
 
 namespace {
@@ -30,13 +31,8 @@ using namespace igw;
 
 constexpr int kChunk = BLOCK;                      // records staged per round: one per thread
 constexpr int kSubs = kChunk / WAVE;
-constexpr int kLvlBytes = IGW_LEVEL_INDEX_BYTES;   // one level block of a colour index (include/igw.h)
-constexpr int kLvlOffs = 16;                       // offs[15] behind the four rotation bounding boxes
-constexpr int kLvlCells = 32;                      // cells[<= 121]: x << 4 | z, sorted by colour class
 constexpr int kChangeOffset = 40;                  // the u16 `change` of a trajectory record
 static_assert(IGW_RELABEL_ROW == STRIDE && IGW_RELABEL_CELLS == CELLS && IGW_RELABEL_RECORD == IGW_TRAJ_BYTES, "layouts of include/igw.h");
-static_assert(kLvlCells + LEVEL <= kLvlBytes && kLvlBytes % 16 == 0, "level index block layout");
-static_assert(HIST_ROW * 2 == WAVE * 16, "a wavefront holds a histogram row as one dwordx4 per lane");
 static_assert(CELLS <= 0x7ff, "a cell fits the low 11 bits of a change");
 
 struct RelabelParams {
@@ -69,27 +65,6 @@ struct Shared {
     alignas(16) uint16_t chg[kChunk];
     WaveShared w[WAVES_PER_BLOCK];
 };
-
-// class + 1 of a synthetic colour in the colour index (0: nothing in a target can match it); a colour outside -7..7
-// clamps to the empty slice behind the last class (include/igw.h)
-__device__ inline int class1(int c) {
-    const int k = min(max(c + 7 + (int)((uint32_t)c >> 31), 0), 15);
-    return c == 0 ? 0 : k;
-}
-
-typedef unsigned short us2 __attribute__((ext_vector_type(2)));
-__device__ inline int row_piece_max(const uint4& v) {
-    const us2 m = __builtin_elementwise_max(
-        __builtin_elementwise_max(__builtin_bit_cast(us2, v.x), __builtin_bit_cast(us2, v.y)),
-        __builtin_elementwise_max(__builtin_bit_cast(us2, v.z), __builtin_bit_cast(us2, v.w)));
-    return (int)max((uint32_t)m.x, (uint32_t)m.y);
-}
-
-__device__ inline int wave_sum_i32(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 __device__ inline double readlane_f64(double v, int l) {
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
@@ -156,37 +131,6 @@ __device__ inline void build_index(const int8_t* tgt_s, const int* bb4, uint8_t*
             if (lane == 0) blk[kLvlOffs + 14] = blk[kLvlOffs + 15] = (uint8_t)off;   // (offs[15] = offs[14]: the empty slice class1() clamps to)
         }
         wave_sync();
-    }
-}
-
-// One change's votes on the histogram row, by the whole wavefront: the target cells of the changed cell's level whose
-// colour is the cell's old synthetic colour lose a vote, those of its new one gain one, per rotation and admissible
-// translation (resolve_changes of igw_kernels.hip, as igw_goal.hip and igw_peek.hip restate it).  Uniform arguments.
-__device__ inline void vote_change(uint32_t* hrow, const uint8_t* index, int cell, int s0, int s1) {
-    const int lane = __lane_id();
-    const int q = lane & 3, mi = lane >> 2;
-    const int lvl = cell / LEVEL, rem = cell - lvl * LEVEL, gx = rem / 11, gz = rem - gx * 11;
-    const uint8_t* blk = index + lvl * kLvlBytes;
-    const int ka = class1(s0), kb = class1(s1);
-    const int oa0 = blk[kLvlOffs - 1 + ka], oa1 = blk[kLvlOffs + ka], ob0 = blk[kLvlOffs - 1 + kb], ob1 = blk[kLvlOffs + kb];
-    const int na = ka != 0 ? oa1 - oa0 : 0, nv = na + (kb != 0 ? ob1 - ob0 : 0);
-    const int bb = (int)reinterpret_cast<const uint32_t*>(blk)[q];
-    const int xmin = (int)(int8_t)(bb & 0xff), dxlo = (int)(int8_t)((bb >> 8) & 0xff) - 10;
-    const int zmin = (int)(int8_t)((bb >> 16) & 0xff), dzlo = (int)(int8_t)((bb >> 24) & 0xff) - 10;
-    for (int i0 = 0; i0 < nv; i0 += WAVE / 4) {   // nv <= 2 * 121
-        const int idx = i0 + mi;
-        if (idx < nv) {
-            const bool dec = idx < na;
-            const int tc = blk[kLvlCells + (dec ? oa0 + idx : ob0 + (idx - na))];
-            const int tx = tc >> 4, tz = tc & 15;
-            const int bx = (q & 1) ? tz : tx, bz = (q & 1) ? tx : tz;
-            const int rx = q >= 2 ? 10 - bx : bx, rz = (q == 1 || q == 2) ? 10 - bz : bz;
-            const int u = rx - gx - dxlo, v = rz - gz - dzlo;
-            if ((unsigned)u <= (unsigned)(xmin - dxlo) && (unsigned)v <= (unsigned)(zmin - dzlo)) {   // (extents <= 10: bins < 484)
-                const int bin = q * LEVEL + u * 11 + v;
-                atomicAdd(&hrow[bin >> 1], (dec ? 0xffffffffu : 1u) << (16 * (bin & 1)));
-            }
-        }
     }
 }
 

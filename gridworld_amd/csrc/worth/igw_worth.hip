@@ -15,7 +15,8 @@
 //   (one ballot over the colour index per env; every level for the breaks and for a task with a starting grid, whose
 //   cells have values of their own) are then worked out a LANE per cell: the lane walks the level's target cells of
 //   v's colour class (a slice of the colour index) and the four rotations, the arithmetic of the step's histogram
-//   update restated below.
+//   update with a lane per cell (the index's layout, class1, row_piece_max and wave_sum_i32 are igw_vote.h's, the query
+//   libraries' one copy).
 //     adding:    m' = max(M, max over the touched admissible bins of h + 1): no copy of the row;
 //     removing:  the touched bins are distinct, so the maximum falls -- to exactly M - 1, every bin that held M now
 //                holds M - 1 and no other held more -- if and only if every bin that holds M is touched: the lane counts
@@ -27,7 +28,7 @@
 // Vector stores only; every loop is static or bounded by the 121 cells of a level times four rotations.
 #include <stdio.h>
 
-#include "../igw_device.h"
+#include "../igw_vote.h"
 #include "../../../include/igw_worth.h"
 
 namespace {
@@ -35,15 +36,10 @@ namespace {
 using namespace igw;
 
 constexpr int kPlanes = IGW_WORTH_PLANES;
-constexpr int kLvlBytes = IGW_LEVEL_INDEX_BYTES;   // one level block of a task's colour index (include/igw.h)
-constexpr int kLvlOffs = 16;                       // offs[15] behind the four rotation bounding boxes
-constexpr int kLvlCells = 32;                      // cells[<= 121]: (x + 5) << 4 | (z + 5), sorted by colour class
 constexpr int kIndexChunks = IGW_TASK_INDEX_BYTES / 16;
 constexpr int kWordChunks = STRIDE * 2 / 16;       // 138 dwordx4 per plane row of int16 words
 constexpr int kNoEdit = 0x7fffffff;
 static_assert(IGW_WORTH_ROW == STRIDE && IGW_WORTH_CELLS == CELLS, "a plane has the layout of a grid row");
-static_assert(kLvlCells + LEVEL <= kLvlBytes && kLvlBytes % 16 == 0 && IGW_TASK_INDEX_BYTES % 16 == 0, "level index block layout");
-static_assert(HIST_ROW * 2 == WAVE * 16, "a wavefront holds a histogram row as one dwordx4 per lane");
 static_assert(kIndexChunks <= 2 * WAVE && kWordChunks <= 3 * WAVE && STRIDE % 8 == 0, "rows in dwordx4 per lane");
 
 struct WorthParams {
@@ -68,27 +64,6 @@ struct WaveShared {
     alignas(16) int8_t start[STRIDE];
     alignas(16) int16_t stage[STRIDE];
 };
-
-// class + 1 of a synthetic colour in the colour index (0: nothing in a target can match it); a colour outside -7..7
-// clamps to the empty slice behind the last class (include/igw.h)
-__device__ inline int class1(int c) {
-    const int k = min(max(c + 7 + (int)((uint32_t)c >> 31), 0), 15);
-    return c == 0 ? 0 : k;
-}
-
-typedef unsigned short us2 __attribute__((ext_vector_type(2)));
-__device__ inline int row_piece_max(const uint4& v) {
-    const us2 m = __builtin_elementwise_max(
-        __builtin_elementwise_max(__builtin_bit_cast(us2, v.x), __builtin_bit_cast(us2, v.y)),
-        __builtin_elementwise_max(__builtin_bit_cast(us2, v.z), __builtin_bit_cast(us2, v.w)));
-    return (int)max((uint32_t)m.x, (uint32_t)m.y);
-}
-
-__device__ inline int wave_sum_i32(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // bit j: byte j of x is 0
 __device__ inline uint32_t zero_bytes(uint32_t x) {

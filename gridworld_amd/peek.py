@@ -22,7 +22,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libigw_peek.so')
 SOURCES = [os.path.join(CSRC, 'peek', 'igw_peek.hip')]
-HEADERS = [os.path.join(CSRC, f) for f in ('igw_device.h', 'igw_trig.h', 'igw_trig_lut.h', 'igw_trig_tables.h')] + \
+HEADERS = [os.path.join(CSRC, f) for f in ('igw_device.h', 'igw_trig.h', 'igw_trig_lut.h', 'igw_trig_tables.h',
+                                            'igw_vote.h', os.path.join('peek', 'igw_peek_core.h'),
+                                            os.path.join('peek', 'igw_peek_body.h'))] + \
           [os.path.join(HERE, '..', 'include', 'igw.h'), os.path.join(HERE, '..', 'include', 'igw_peek.h')]
 VERSION = 1
 ACTIONS = 18

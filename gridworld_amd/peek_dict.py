@@ -21,7 +21,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libigw_peek_dict.so')
 SOURCES = [os.path.join(CSRC, 'peek_dict', 'igw_peek_dict.hip')]
-HEADERS = [os.path.join(CSRC, f) for f in ('igw_device.h', 'igw_trig.h', 'igw_trig_lut.h', 'igw_trig_tables.h')] + \
+HEADERS = [os.path.join(CSRC, f) for f in ('igw_device.h', 'igw_trig.h', 'igw_trig_lut.h', 'igw_trig_tables.h',
+                                            'igw_vote.h', os.path.join('peek', 'igw_peek_core.h'),
+                                            os.path.join('peek', 'igw_peek_body.h'))] + \
           [os.path.join(HERE, '..', 'include', f) for f in ('igw.h', 'igw_peek.h', 'igw_peek_dict.h')]
 VERSION = 1
 MAX_H = _peek.MAX_H

@@ -278,6 +278,32 @@ def test_chunk_and_step_boundaries(space, K, H):
         assert torch.equal(part['ret'].view(torch.int32), whole['ret'][:, :K].view(torch.int32))
 
 
+def test_discrete_actions_through_peek_and_through_the_walking_dict_entry_agree_bitwise():
+    """One kernel body serves igw_peek and igw_peek_walking_dict: three envs of `towers` after 12 steps, K = 65 (a
+    64-chunk plus one candidate) per-env sequences of H = 4 random Discrete(18) actions through env.peek, the same
+    actions as buttons and camera through peek_dict of a walking Dict batch in the same state.  All five outputs, float32
+    as bit patterns."""
+    n, K, H, T0 = 3, 65, 4, 12
+    acts = np.random.default_rng(2365).integers(0, 18, (n, K, H)).astype(np.int32)
+    res = {}
+    for space in ('discrete', 'walking_dict'):
+        c = (DC.PC.cases() if space == 'discrete' else DC.cases(space))['towers']
+        cut = lambda a: None if a is None else a[:n]  # noqa: E731
+        env = _gpu_env(dict(c, targets=c['targets'][:n], starts=cut(c['starts']), poses=cut(c['poses'])))
+        env.reset()
+        for t in range(T0):
+            a = c['actions'][t, :n]
+            env.step(torch.from_numpy(np.array(a)).to(env.device) if space == 'discrete' else _dev(DC.from_discrete(space, a), env))
+        res[space] = env.peek(torch.from_numpy(acts).to(env.device), gamma=0.97) if space == 'discrete' else \
+            env.peek_dict(_dev(DC.from_discrete(space, acts), env), gamma=0.97)
+        assert tuple(res[space]['reward'].shape) == (n, K, H)
+    a, b = _np(res['discrete']), _np(res['walking_dict'])
+    bad = _mismatches(a, b)
+    print(f'{int((a["change"] >= 0).sum())} changes, {int((a["reward"] != 0).sum())} rewards that are not 0; elements that differ: {bad}')
+    assert (a['change'] >= 0).sum() >= 20 and (a['reward'] != 0).sum() >= 20
+    assert not any(bad.values())
+
+
 def _edge(space, n, seed, steps, k, h, shared=False):
     """(env, candidates, truth) of n rt20 envs of the space after `steps` steps of a random stream."""
     from gridworld_amd import workloads

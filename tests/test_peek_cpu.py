@@ -52,11 +52,15 @@ def test_peek_sources_are_in_no_other_library():
     assert P.LIBRARY.flags == () and os.path.basename(P.LIB) == 'libigw_peek.so'
     assert P.LIBRARY.marker == b'igw-peek-build-id:'
     assert P.LIBRARY.marker not in (Q.LIBRARY.marker, G.LIBRARY.marker, A.LIBRARY.marker, B.STEP.marker)
-    text = open(P.SOURCES[0]).read()
+    # the library's own files: its .hip file, the headers under csrc/peek/ and igw_vote.h
+    own = [s for s in P.SOURCES + P.HEADERS if os.path.basename(os.path.dirname(s)) == 'peek' or os.path.basename(s) == 'igw_vote.h']
+    assert sorted(os.path.basename(s) for s in own) == ['igw_peek.hip', 'igw_peek_body.h', 'igw_peek_core.h', 'igw_vote.h']
+    text = ''.join(open(s).read() for s in own)
     assert '#include "../igw_device.h"' in text
     for name in ('parse_walking_discrete', 'world_act_pre', 'world_act_post', 'finish_break', 'world_update',
                  'syn_size_delta', 'finish_step'):
         assert re.search(r'\b%s\(' % name, text), name   # restated here, not moved out of the step library
+    assert not {'igw_peek_body.h', 'igw_peek_core.h', 'igw_vote.h'} & {os.path.basename(s) for s in B.SOURCES + B.HEADERS}
 
 
 def test_peek_code_object_has_no_scratch_and_no_vector_spills(tmp_path):

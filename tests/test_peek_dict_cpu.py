@@ -79,7 +79,12 @@ def test_sources_are_in_no_other_library():
     assert D.LIBRARY.flags == () and D.LIBRARY.marker == b'igw-peek-dict-build-id:'
     assert D.LIBRARY.marker not in (P.LIBRARY.marker, Q.LIBRARY.marker, G.LIBRARY.marker, A.LIBRARY.marker, B.STEP.marker)
     assert P.LIBRARY.marker not in open(D.build(), 'rb').read()   # (... nor is it a prefix that built_id could find there)
-    text = open(D.SOURCES[0]).read()
+    # the library's own files: its .hip file, the headers under csrc/peek/ and igw_vote.h
+    own = [s for s in D.SOURCES + D.HEADERS
+           if os.path.basename(os.path.dirname(s)) in ('peek', 'peek_dict') or os.path.basename(s) == 'igw_vote.h']
+    assert sorted(os.path.basename(s) for s in own) == ['igw_peek_body.h', 'igw_peek_core.h', 'igw_peek_dict.hip', 'igw_vote.h']
+    assert not {'igw_peek_body.h', 'igw_peek_core.h', 'igw_vote.h'} & {os.path.basename(s) for s in B.SOURCES + B.HEADERS}
+    text = ''.join(open(s).read() for s in own)
     assert '#include "../igw_device.h"' in text and 'igw_trig.h' in open(os.path.join(D.CSRC, 'igw_device.h')).read()
     for name in ('igw_sincos', 'dd_two_prod', 'igw_atan2_accurate'):
         assert not re.search(r'\b%s\s*\([^;{]*\)\s*\{' % name, text), name   # the trig is included, not copied
