@@ -11,47 +11,32 @@ the step library's profiles stay valid).  There is no CPU fallback: without a HI
 raises.
 """
 import ctypes as C
-import os
 import sys
 
+from . import _out
 from . import build as _build
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-CSRC = os.path.join(HERE, 'csrc')
-LIB = os.path.join(HERE, 'libigw_aim.so')
-SOURCES = [os.path.join(CSRC, 'aim', 'igw_aim.hip')]
-HEADERS = [os.path.join(CSRC, f) for f in ('igw_device.h', 'igw_trig.h', 'igw_trig_lut.h', 'igw_trig_tables.h')] + \
-          [os.path.join(HERE, '..', 'include', 'igw.h'), os.path.join(HERE, '..', 'include', 'igw_aim.h')]
 VERSION = 1
 ROW = 1104          # int32 words per env and plane
 CELLS = 1089
 MAX_TURNS = 72
 HALF = 36           # di = -36..35, dj = -36..36; a code holds di + 36 and dj + 36
 NONE = -1
+OUTPUTS = ('place', 'break')   # in the order igw_aim takes them
 _vp, _i32 = C.c_void_p, C.c_int32
-# every symbol include/igw_aim.h declares: (result, arguments)
-SIGNATURES = {
-    'igw_aim_version': (C.c_int, []),
-    'igw_aim_build_id': (C.c_char_p, []),
-    'igw_aim_last_error': (C.c_char_p, []),
-    'igw_aim': (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp]),
-}
-EXPORTS = list(SIGNATURES)
-LIBRARY = _build.Library(LIB, SOURCES, HEADERS, 'igw-aim-build-id:', 'IGW_AIM_BUILD_ID', deps=[__file__])
-source_hash, built_id, is_stale = LIBRARY.source_hash, LIBRARY.built_id, LIBRARY.is_stale
 
 
 class AimError(RuntimeError):
     pass
 
 
-def build(force=False, verbose=False):
-    """Builds libigw_aim.so; returns its path."""
-    return LIBRARY.build(force, verbose=verbose)
-
-
-BINDING = _build.Binding(LIBRARY, SIGNATURES, AimError, 'igw_aim_last_error', 'igw_aim_build_id',
-                         'gridworld_amd.aim', 'igw_aim')
+# include/igw_aim.h declares igw_aim and the three symbols every library has: (result, arguments)
+LIBRARY, BINDING = _build.query('aim', __file__, {
+    'igw_aim': (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp]),
+}, AimError, 'igw_aim')
+LIB, SOURCES, HEADERS = LIBRARY.lib, LIBRARY.sources, LIBRARY.headers
+SIGNATURES, EXPORTS = BINDING.signatures, list(BINDING.signatures)
+build, source_hash, built_id, is_stale = LIBRARY.build, LIBRARY.source_hash, LIBRARY.built_id, LIBRARY.is_stale
 load, check, build_id = BINDING.load, BINDING.check, BINDING.build_id
 
 
@@ -62,12 +47,16 @@ def aim_into(agent, occ, n, max_turns, place, brk, stream):
         BINDING.check(rc, 'igw_aim')
 
 
-def plane(n, dev, stream=None):
-    """A new output plane as aim() returns it: an int32 [n, 9, 11, 11] view of 1104-word rows."""
+def _specs(n):
+    """name -> _out.spec of a plane: an int32 [n, 9, 11, 11] view of 1104-word rows, 16-byte aligned."""
     import torch
-    with torch.cuda.stream(stream):
-        base = torch.empty((n, ROW), dtype=torch.int32, device=dev)
-    return torch.as_strided(base, (n, 9, 11, 11), (ROW, 121, 11, 1))
+    plane = _out.spec((n, 9, 11, 11), torch.int32, (ROW, 121, 11, 1), 16, (n, ROW))
+    return {'place': plane, 'break': plane}
+
+
+def plane(n, dev, stream=None):
+    """A new output plane as aim() returns it."""
+    return _out.outputs('aim', OUTPUTS, ('place',), _specs(n), None, dev, stream)[0]['place']
 
 
 def launch(agent, occ, n, max_turns, place, brk, out, dev, stream, alloc_stream=None):
@@ -75,28 +64,14 @@ def launch(agent, occ, n, max_turns, place, brk, out, dev, stream, alloc_stream=
     `occ` are the state tensors' rows; place / brk are bools; `out` (a dict or None) holds planes to write, as an
     earlier call returned them; what it lacks is allocated, so with every plane given nothing is.  It touches the
     device only through data_ptr() and the ctypes call."""
-    import torch
     if not 0 <= int(max_turns) <= MAX_TURNS:
         raise ValueError(f'max_turns must be 0..{MAX_TURNS}, not {max_turns}')
     names = [k for k, w in (('place', place), ('break', brk)) if w]
     if not names:
         raise ValueError('aim: place and brk are both off, nothing to compute')
-    out = dict(out or {})
-    unknown = [k for k in out if k not in names]
-    if unknown:
-        raise ValueError(f'out holds {unknown}, the call writes {names}')
-    shape, strides = (n, 9, 11, 11), (ROW, 121, 11, 1)
-    for k, t in out.items():
-        if (not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != torch.int32 or t.device != dev
-                or (n > 0 and tuple(t.stride()) != strides) or t.data_ptr() % 16):
-            raise ValueError(f'out[{k!r}] must be an int32 tensor {shape} with strides {strides} on {dev}, 16-byte '
-                             'aligned (what aim() returns)')
-    for k in names:
-        if k not in out:
-            out[k] = plane(n, dev, alloc_stream)
-    ptr = lambda k: out[k].data_ptr() if k in out else None  # noqa: E731
-    aim_into(agent.data_ptr(), occ.data_ptr(), n, max_turns, ptr('place'), ptr('break'), stream)
-    return {k: out[k] for k in names}
+    res, ptrs = _out.outputs('aim', OUTPUTS, names, _specs(n), out, dev, alloc_stream)
+    aim_into(agent.data_ptr(), occ.data_ptr(), n, max_turns, *ptrs, stream)
+    return res
 
 
 def aim_decode(code):

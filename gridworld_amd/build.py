@@ -1,7 +1,7 @@
 """Builds gridworld_amd/libigw_hip.so (HIP kernels + C ABI) for gfx950 with hipcc.
 
     python -m gridworld_amd.build            # build if stale: the step library, then the render, codec, query, goal,
-    python -m gridworld_amd.build --force    # aim, peek, peek_dict, vox, worth and relabel libraries (each module's own build())
+    python -m gridworld_amd.build --force    # aim, peek, peek_dict, vox, worth, relabel and recall libraries (each module's own build())
 
 hipcc cross-compiles without a GPU.  -ffp-contract=off is REQUIRED: the reference computes
 in IEEE binary64 with one rounding per operation; never add fast-math flags.
@@ -153,6 +153,29 @@ class Binding:
             raise self.error(f'{what or self.what} failed ({code}): {msg.decode() if msg else ""}')
 
 
+# What a library that reads the step path's state includes: the device headers and the step ABI (absolute paths, as a
+# query module's own files are).
+DEVICE_HEADERS = [os.path.join(CSRC, f) for f in ('igw_device.h', 'igw_trig.h', 'igw_trig_lut.h', 'igw_trig_tables.h')] + \
+                 [os.path.join(HERE, '..', 'include', 'igw.h')]
+
+
+def query(name, module_file, signatures, error, what, headers=(), include=(), device=True):
+    """(Library, Binding) of the query library `name`: libigw_<name>.so from csrc/<name>/igw_<name>.hip, the headers
+    `headers` under csrc and include/igw_<name>.h (after `include`, further ones of include/) -- behind DEVICE_HEADERS
+    when the kernels read the step path's state.  `signatures` are the entry points; the three symbols every library has
+    (igw_<name>_version / _build_id / _last_error) are put in front of them.  `error` is what the binding raises, `what`
+    the entry check() names by default, `module_file` the describing module: the library is stale when that file or this
+    one is newer."""
+    sym = 'igw_' + name
+    lib = Library(os.path.join(HERE, f'lib{sym}.so'), [os.path.join(CSRC, name, sym + '.hip')],
+                  (DEVICE_HEADERS if device else []) + [os.path.join(CSRC, f) for f in headers] +
+                  [os.path.join(HERE, '..', 'include', f) for f in (*include, sym + '.h')],
+                  f'igw-{name.replace("_", "-")}-build-id:', f'IGW_{name.upper()}_BUILD_ID', deps=[module_file, __file__])
+    signatures = {sym + '_version': (ctypes.c_int, []), sym + '_build_id': (ctypes.c_char_p, []),
+                  sym + '_last_error': (ctypes.c_char_p, []), **signatures}
+    return lib, Binding(lib, signatures, error, sym + '_last_error', sym + '_build_id', 'gridworld_amd.' + name, what)
+
+
 # The step library and its diagnostic variant (libigw_hip_diag.so, -DIGW_DIAG, next to the production library).  The
 # id is compiled into the library (-DIGW_BUILD_ID, exported as igw_build_id()) and stamped on every profile summary
 # under profiles/ (tools/summarize_profile.py), so a bench line can tell whether the PMC bytes it quotes were measured
@@ -181,8 +204,6 @@ def build(force=False, extra_flags=(), verbose=False, diag=False):
 if __name__ == '__main__':
     print(build(force='--force' in sys.argv, verbose=True, diag='--diag' in sys.argv))
     if '--diag' not in sys.argv:   # ... and the libraries beside the step library, each by its own module's build()
-        from . import aim, codec, goal, peek, peek_dict, query, relabel, render, vox, worth
-        for module in (render, codec, query, goal, aim, peek, peek_dict, vox, worth, relabel):
+        from . import aim, codec, goal, peek, peek_dict, query, recall, relabel, render, vox, worth
+        for module in (render, codec, query, goal, aim, peek, peek_dict, vox, worth, relabel, recall):
             print(module.build(force='--force' in sys.argv))
-        from . import recall   # ... and the recall query's
-        print(recall.build(force='--force' in sys.argv))

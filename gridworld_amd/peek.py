@@ -13,50 +13,35 @@ own, so the step library's profiles stay valid).  There is no CPU fallback: with
 the call raises.
 """
 import ctypes as C
-import os
+import functools
 import sys
 
+from . import _out
 from . import build as _build
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-CSRC = os.path.join(HERE, 'csrc')
-LIB = os.path.join(HERE, 'libigw_peek.so')
-SOURCES = [os.path.join(CSRC, 'peek', 'igw_peek.hip')]
-HEADERS = [os.path.join(CSRC, f) for f in ('igw_device.h', 'igw_trig.h', 'igw_trig_lut.h', 'igw_trig_tables.h',
-                                            'igw_vote.h', os.path.join('peek', 'igw_peek_core.h'),
-                                            os.path.join('peek', 'igw_peek_body.h'))] + \
-          [os.path.join(HERE, '..', 'include', 'igw.h'), os.path.join(HERE, '..', 'include', 'igw_peek.h')]
 VERSION = 1
 ACTIONS = 18
 MAX_H = 32
 MAX_K = 4096
 OUTPUTS = ('reward', 'ends', 'change', 'pose', 'ret')   # in the order igw_peek takes them
 NONE = -1
+SHARED_HEADERS = ['igw_vote.h', 'peek/igw_peek_core.h', 'peek/igw_peek_body.h']   # the kernel, as peek_dict builds it too
 _vp, _i32, _f64 = C.c_void_p, C.c_int32, C.c_double
-# every symbol include/igw_peek.h declares: (result, arguments)
-SIGNATURES = {
-    'igw_peek_version': (C.c_int, []),
-    'igw_peek_build_id': (C.c_char_p, []),
-    'igw_peek_last_error': (C.c_char_p, []),
-    'igw_peek': (C.c_int, [_vp] * 9 + [_i32, _i32, _i32, _vp, _i32, _f64, _f64, _i32, _i32, _f64] + [_vp] * 6),
-}
-EXPORTS = list(SIGNATURES)
-LIBRARY = _build.Library(LIB, SOURCES, HEADERS, 'igw-peek-build-id:', 'IGW_PEEK_BUILD_ID', deps=[__file__])
-source_hash, built_id, is_stale = LIBRARY.source_hash, LIBRARY.built_id, LIBRARY.is_stale
 
 
 class PeekError(RuntimeError):
     pass
 
 
-def build(force=False, verbose=False):
-    """Builds libigw_peek.so; returns its path."""
-    return LIBRARY.build(force, verbose=verbose)
-
-
-BINDING = _build.Binding(LIBRARY, SIGNATURES, PeekError, 'igw_peek_last_error', 'igw_peek_build_id',
-                         'gridworld_amd.peek', 'igw_peek')
+# include/igw_peek.h declares igw_peek and the three symbols every library has: (result, arguments)
+LIBRARY, BINDING = _build.query('peek', __file__, {
+    'igw_peek': (C.c_int, [_vp] * 9 + [_i32, _i32, _i32, _vp, _i32, _f64, _f64, _i32, _i32, _f64] + [_vp] * 6),
+}, PeekError, 'igw_peek', headers=SHARED_HEADERS)
+LIB, SOURCES, HEADERS = LIBRARY.lib, LIBRARY.sources, LIBRARY.headers
+SIGNATURES, EXPORTS = BINDING.signatures, list(BINDING.signatures)
+build, source_hash, built_id, is_stale = LIBRARY.build, LIBRARY.source_hash, LIBRARY.built_id, LIBRARY.is_stale
 load, check, build_id = BINDING.load, BINDING.check, BINDING.build_id
+check_outputs = functools.partial(_out.check_outputs, 'peek', OUTPUTS, string=False)
 
 
 def peek_into(state, n, k, h, actions, per_env, right_scale, wrong_scale, max_steps, select_and_place, gamma, outputs,
@@ -86,20 +71,12 @@ def shape_of(actions, n):
     return k, h, len(shape) == 3
 
 
-def check_outputs(names):
-    """The outputs asked for, in OUTPUTS' order; ValueError for none or an unknown one."""
-    names = tuple(names)
-    unknown = [k for k in names if k not in OUTPUTS]
-    if unknown or not names:
-        raise ValueError(f'peek: outputs names some of {OUTPUTS}, at least one, got {names!r}')
-    return tuple(k for k in OUTPUTS if k in names)
-
-
 def _specs(n, k, h):
-    """name -> (shape, dtype) of the contiguous tensor a caller sees."""
+    """name -> _out.spec of the contiguous tensor a caller sees."""
     import torch
-    return {'reward': ((n, k, h), torch.float32), 'ends': ((n, k), torch.int16), 'change': ((n, k, h), torch.int16),
-            'pose': ((n, k, 5), torch.float32), 'ret': ((n, k), torch.float32)}
+    return {'reward': _out.spec((n, k, h), torch.float32), 'ends': _out.spec((n, k), torch.int16),
+            'change': _out.spec((n, k, h), torch.int16), 'pose': _out.spec((n, k, 5), torch.float32),
+            'ret': _out.spec((n, k), torch.float32)}
 
 
 def launch(state, n, actions, reward, gamma, names, out, dev, stream, alloc_stream=None):
@@ -108,27 +85,11 @@ def launch(state, n, actions, reward, gamma, names, out, dev, stream, alloc_stre
     (right_scale, wrong_scale, max_steps, select_and_place).  `out` (a dict or None) holds tensors to write, as an
     earlier call returned them; what it lacks is allocated, so with every output given nothing is.  It touches the
     device only through data_ptr() and the ctypes call."""
-    import torch
     names = check_outputs(names)
     k, h, per_env = shape_of(actions, n)
-    out = dict(out or {})
-    unknown = [key for key in out if key not in names]
-    if unknown:
-        raise ValueError(f'out holds {unknown}, the call writes {list(names)}')
-    specs = _specs(n, k, h)
-    for key, t in out.items():
-        shape, dtype = specs[key]
-        if (not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dtype or t.device != dev
-                or not t.is_contiguous()):
-            raise ValueError(f'out[{key!r}] must be a contiguous {dtype} tensor {shape} on {dev} (what peek() returns)')
-    with torch.cuda.stream(alloc_stream):
-        for key in names:
-            if key not in out:
-                out[key] = torch.empty(specs[key][0], dtype=specs[key][1], device=dev)
-    ptr = lambda key: out[key].data_ptr() if key in names else None  # noqa: E731
-    peek_into([t.data_ptr() for t in state], n, k, h, actions.data_ptr(), per_env, *reward, gamma,
-              [ptr(key) for key in OUTPUTS], stream)
-    return {key: out[key] for key in names}
+    res, ptrs = _out.outputs('peek', OUTPUTS, names, _specs(n, k, h), out, dev, alloc_stream)
+    peek_into([t.data_ptr() for t in state], n, k, h, actions.data_ptr(), per_env, *reward, gamma, ptrs, stream)
+    return res
 
 
 def peek_decode(change):

@@ -11,20 +11,14 @@ The library is a separate one beside libigw_peek.so (the Discrete(18) space): it
 the peek library's stay valid).  There is no CPU fallback: without a HIP device the launch fails and the call raises.
 """
 import ctypes as C
-import os
+import functools
 import sys
 
+from . import _out
 from . import build as _build
 from . import peek as _peek
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-CSRC = os.path.join(HERE, 'csrc')
-LIB = os.path.join(HERE, 'libigw_peek_dict.so')
-SOURCES = [os.path.join(CSRC, 'peek_dict', 'igw_peek_dict.hip')]
-HEADERS = [os.path.join(CSRC, f) for f in ('igw_device.h', 'igw_trig.h', 'igw_trig_lut.h', 'igw_trig_tables.h',
-                                            'igw_vote.h', os.path.join('peek', 'igw_peek_core.h'),
-                                            os.path.join('peek', 'igw_peek_body.h'))] + \
-          [os.path.join(HERE, '..', 'include', f) for f in ('igw.h', 'igw_peek.h', 'igw_peek_dict.h')]
+CSRC = _build.CSRC
 VERSION = 1
 MAX_H = _peek.MAX_H
 MAX_K = _peek.MAX_K
@@ -37,31 +31,22 @@ SPACES = {
 }
 _vp, _i32, _f64 = C.c_void_p, C.c_int32, C.c_double
 _tail = [_i32, _f64, _f64, _i32, _i32, _f64] + [_vp] * 6   # per_env .. gamma, the five outputs, the stream
-# every symbol include/igw_peek_dict.h declares: (result, arguments)
-SIGNATURES = {
-    'igw_peek_dict_version': (C.c_int, []),
-    'igw_peek_dict_build_id': (C.c_char_p, []),
-    'igw_peek_dict_last_error': (C.c_char_p, []),
-    'igw_peek_flying': (C.c_int, [_vp] * 9 + [_i32, _i32, _i32] + [_vp] * 4 + _tail),
-    'igw_peek_walking_dict': (C.c_int, [_vp] * 9 + [_i32, _i32, _i32] + [_vp] * 2 + _tail),
-}
-EXPORTS = list(SIGNATURES)
-LIBRARY = _build.Library(LIB, SOURCES, HEADERS, 'igw-peek-dict-build-id:', 'IGW_PEEK_DICT_BUILD_ID', deps=[__file__])
-source_hash, built_id, is_stale = LIBRARY.source_hash, LIBRARY.built_id, LIBRARY.is_stale
 
 
 class PeekDictError(RuntimeError):
     pass
 
 
-def build(force=False, verbose=False):
-    """Builds libigw_peek_dict.so; returns its path."""
-    return LIBRARY.build(force, verbose=verbose)
-
-
-BINDING = _build.Binding(LIBRARY, SIGNATURES, PeekDictError, 'igw_peek_dict_last_error', 'igw_peek_dict_build_id',
-                         'gridworld_amd.peek_dict', 'igw_peek_dict')
+# include/igw_peek_dict.h declares the two entries and the three symbols every library has: (result, arguments)
+LIBRARY, BINDING = _build.query('peek_dict', __file__, {
+    'igw_peek_flying': (C.c_int, [_vp] * 9 + [_i32, _i32, _i32] + [_vp] * 4 + _tail),
+    'igw_peek_walking_dict': (C.c_int, [_vp] * 9 + [_i32, _i32, _i32] + [_vp] * 2 + _tail),
+}, PeekDictError, 'igw_peek_dict', headers=_peek.SHARED_HEADERS, include=['igw_peek.h'])
+LIB, SOURCES, HEADERS = LIBRARY.lib, LIBRARY.sources, LIBRARY.headers
+SIGNATURES, EXPORTS = BINDING.signatures, list(BINDING.signatures)
+build, source_hash, built_id, is_stale = LIBRARY.build, LIBRARY.source_hash, LIBRARY.built_id, LIBRARY.is_stale
 load, check, build_id = BINDING.load, BINDING.check, BINDING.build_id
+check_outputs = functools.partial(_out.check_outputs, 'peek_dict', OUTPUTS, string=False)
 
 
 def peek_into(space, state, n, k, h, actions, per_env, right_scale, wrong_scale, max_steps, select_and_place, gamma,
@@ -111,15 +96,6 @@ def shape_of(space, actions, n):
     return k, h, len(lead) == 3
 
 
-def check_outputs(names):
-    """The outputs asked for, in OUTPUTS' order; ValueError for none or an unknown one."""
-    names = tuple(names)
-    unknown = [k for k in names if k not in OUTPUTS]
-    if unknown or not names:
-        raise ValueError(f'peek_dict: outputs names some of {OUTPUTS}, at least one, got {names!r}')
-    return tuple(k for k in OUTPUTS if k in names)
-
-
 def device_actions(space, actions, dev):
     """The space's action entries as contiguous device tensors of the ABI dtypes, in the entry's order: an entry that
     already is one is passed on as it is, anything else (arrays, lists, other dtypes or devices, strided views) is
@@ -155,26 +131,12 @@ def launch(space, state, n, actions, reward, gamma, names, out, dev, stream, all
     import torch
     names = check_outputs(names)
     k, h, per_env = shape_of(space, actions, n)
-    out = dict(out or {})
-    unknown = [key for key in out if key not in names]
-    if unknown:
-        raise ValueError(f'out holds {unknown}, the call writes {list(names)}')
-    specs = _peek._specs(n, k, h)
-    for key, t in out.items():
-        shape, dtype = specs[key]
-        if (not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dtype or t.device != dev
-                or not t.is_contiguous()):
-            raise ValueError(f'out[{key!r}] must be a contiguous {dtype} tensor {shape} on {dev} (what peek_dict() '
-                             'returns)')
+    res, ptrs = _out.outputs('peek_dict', OUTPUTS, names, _peek._specs(n, k, h), out, dev, alloc_stream)
     with torch.cuda.stream(alloc_stream):
         bufs = device_actions(space, actions, dev)
-        for key in names:
-            if key not in out:
-                out[key] = torch.empty(specs[key][0], dtype=specs[key][1], device=dev)
-    ptr = lambda key: out[key].data_ptr() if key in names else None  # noqa: E731
-    peek_into(space, [t.data_ptr() for t in state], n, k, h, [b.data_ptr() for b in bufs], per_env, *reward, gamma,
-              [ptr(key) for key in OUTPUTS], stream)
-    return {key: out[key] for key in names}, bufs
+    peek_into(space, [t.data_ptr() for t in state], n, k, h, [b.data_ptr() for b in bufs], per_env, *reward, gamma, ptrs,
+              stream)
+    return res, bufs
 
 
 if __name__ == '__main__':

@@ -12,17 +12,14 @@ step library's build (its sources and build id are its own, so the step library'
 CPU fallback: without a HIP device the launch fails and the call raises.
 """
 import ctypes as C
-import os
+import functools
 import sys
 
+from . import _out
 from . import build as _build
 from . import vox as _vox
+from ._out import _is
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-CSRC = os.path.join(HERE, 'csrc')
-LIB = os.path.join(HERE, 'libigw_recall.so')
-SOURCES = [os.path.join(CSRC, 'recall', 'igw_recall.hip')]
-HEADERS = [os.path.join(HERE, '..', 'include', 'igw_recall.h')]
 VERSION = 1
 ROW = 1104          # bytes of a grid row
 CELLS = 1089
@@ -49,31 +46,21 @@ class Spec(C.Structure):
                 ('radius', _i32), ('dtype', _i32), ('stack', _i32), ('scale', C.c_float), ('bias', C.c_float)]
 
 
-# every symbol include/igw_recall.h declares: (result, arguments)
-SIGNATURES = {
-    'igw_recall_version': (C.c_int, []),
-    'igw_recall_build_id': (C.c_char_p, []),
-    'igw_recall_last_error': (C.c_char_p, []),
-    'igw_recall': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _i64, _i64, _vp,
-                             C.POINTER(Spec), _vp, _vp, _vp, _vp, _vp]),
-}
-EXPORTS = list(SIGNATURES)
-LIBRARY = _build.Library(LIB, SOURCES, HEADERS, 'igw-recall-build-id:', 'IGW_RECALL_BUILD_ID', deps=[__file__])
-source_hash, built_id, is_stale = LIBRARY.source_hash, LIBRARY.built_id, LIBRARY.is_stale
-
-
 class RecallError(RuntimeError):
     pass
 
 
-def build(force=False, verbose=False):
-    """Builds libigw_recall.so; returns its path."""
-    return LIBRARY.build(force, verbose=verbose)
-
-
-BINDING = _build.Binding(LIBRARY, SIGNATURES, RecallError, 'igw_recall_last_error', 'igw_recall_build_id',
-                         'gridworld_amd.recall', 'igw_recall')
+# include/igw_recall.h declares igw_recall and the three symbols every library has: (result, arguments)
+LIBRARY, BINDING = _build.query('recall', __file__, {
+    'igw_recall': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _i64, _i64, _vp,
+                             C.POINTER(Spec), _vp, _vp, _vp, _vp, _vp]),
+}, RecallError, 'igw_recall', device=False)
+LIB, SOURCES, HEADERS = LIBRARY.lib, LIBRARY.sources, LIBRARY.headers
+SIGNATURES, EXPORTS = BINDING.signatures, list(BINDING.signatures)
+build, source_hash, built_id, is_stale = LIBRARY.build, LIBRARY.source_hash, LIBRARY.built_id, LIBRARY.is_stale
 load, check, build_id = BINDING.load, BINDING.check, BINDING.build_id
+check_outputs = functools.partial(_out.check_outputs, 'recall', OUTPUTS)
+grid_rows = functools.partial(_out.grid_rows, 'recall: starts')
 
 
 def spec_of(spec):
@@ -107,27 +94,17 @@ def recall_into(records, n_records, first, length, starts, init_pose, e, l, epis
         BINDING.check(rc, 'igw_recall')
 
 
-def check_outputs(outputs):
-    """The outputs named, in the library's order; ValueError for none or an unknown one."""
-    names = (outputs,) if isinstance(outputs, str) else tuple(outputs)
-    unknown = [k for k in names if k not in OUTPUTS]
-    if unknown or not names:
-        raise ValueError(f'recall: outputs names one or more of {OUTPUTS}, got {outputs!r}')
-    return tuple(k for k in OUTPUTS if k in names)
-
-
 def _specs(spec, b):
-    """name -> (shape, dtype) of the tensor a caller sees."""
+    """name -> _out.spec of the contiguous tensor a caller sees; `record` is 4-byte aligned (decode() views it)."""
     import torch
-    return {'obs': (spec.shape(b), spec.dtype), 'next_obs': (spec.shape(b), spec.dtype),
-            'record': ((b, RECORD), torch.uint8), 'valid': ((b,), torch.uint8)}
+    obs = _out.spec(spec.shape(b), spec.dtype)
+    return {'obs': obs, 'next_obs': obs, 'record': _out.spec((b, RECORD), torch.uint8, align=4),
+            'valid': _out.spec((b,), torch.uint8)}
 
 
 def outputs(spec, b, names, dev, stream=None):
     """New tensors for the outputs `names`, as recall() returns them."""
-    import torch
-    with torch.cuda.stream(stream):
-        return {k: torch.empty(_specs(spec, b)[k][0], dtype=_specs(spec, b)[k][1], device=dev) for k in names}
+    return _out.outputs('recall', OUTPUTS, names, _specs(spec, b), None, dev, stream)[0]
 
 
 def goal_rows(t):
@@ -179,12 +156,6 @@ def decode(record, space='walking'):
     return res
 
 
-def _is(t, dtype, shape, dev):
-    import torch
-    return (torch.is_tensor(t) and t.dtype == dtype and tuple(t.shape) == tuple(shape) and t.device == dev
-            and t.is_contiguous())
-
-
 def launch(records, first, length, starts, init_pose, episode, step, spec, goal, goal_index, cap, names, out, dev, stream,
            alloc_stream=None, space='walking'):
     """One igw_recall launch; returns the dict name -> tensor of `names` (a subset of OUTPUTS) plus decode()'s views of
@@ -222,45 +193,14 @@ def launch(records, first, length, starts, init_pose, episode, step, spec, goal,
         raise ValueError("recall: a 'target' plane reads the goal rows: pass goal=")
     if goal_index is not None and (goal is None or not _is(goal_index, torch.int64, (b,), dev)):
         raise ValueError(f'recall: goal_index goes with goal and must be an int64 tensor [{b}] on {dev}')
-    out = dict(out or {})
-    unknown = [k for k in out if k not in names]
-    if unknown:
-        raise ValueError(f'out holds {unknown}, the call writes {list(names)}')
-    specs = _specs(spec, b)
-    for k, t in out.items():
-        shape, dtype = specs[k]
-        if (not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dtype or t.device != dev
-                or not t.is_contiguous() or (k == 'record' and t.data_ptr() % 4)):
-            raise ValueError(f'out[{k!r}] must be a contiguous {dtype} tensor {shape} on {dev} (what recall() returns; '
-                             'record 4-byte aligned)')
-    out.update(outputs(spec, b, [k for k in names if k not in out], dev, alloc_stream))
+    res, ptrs = _out.outputs('recall', OUTPUTS, names, _specs(spec, b), out, dev, alloc_stream)
     if b:   # (the tensors of no sample have no address to pass)
         recall_into(records.data_ptr(), records.numel() // RECORD, first.data_ptr(), length.data_ptr(), starts.data_ptr(),
                     init_pose.data_ptr(), e, min(int(cap), NO_CLAMP), episode.data_ptr(), step.data_ptr(), b, gptr, gstride,
-                    grows, None if goal_index is None else goal_index.data_ptr(), s,
-                    [out[k].data_ptr() if k in names else None for k in OUTPUTS], stream)
-    res = {k: out[k] for k in names}
+                    grows, _out.ptr(goal_index), s, ptrs, stream)
     if 'record' in res:
         res.update(decode(res['record'], space))
     return res
-
-
-def grid_rows(x, dev, lead):
-    """An integer tensor or array [*lead, 9, 11, 11], [*lead, 1089] or [*lead, 1104] -> a contiguous int8 device tensor
-    [*lead, 1104] (the one given, if it is that already)."""
-    import numpy as np
-    import torch
-    t = x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))
-    lead = tuple(lead)
-    if tuple(t.shape) == lead + (9, 11, 11):
-        t = t.reshape(lead + (CELLS,))
-    if tuple(t.shape) == lead + (ROW,):
-        return t.to(device=dev, dtype=torch.int8).contiguous()
-    if tuple(t.shape) != lead + (CELLS,):
-        raise ValueError(f'recall: starts must be {lead + (9, 11, 11)}, {lead + (CELLS,)} or {lead + (ROW,)}, got {tuple(t.shape)}')
-    rows = torch.zeros(lead + (ROW,), dtype=torch.int8, device=dev)
-    rows[..., :CELLS] = t.to(device=dev, dtype=torch.int8)
-    return rows
 
 
 def recall(records, first, length, starts, init_pose, episode, step, spec, goal=None, goal_index=None, outputs=DEFAULT,

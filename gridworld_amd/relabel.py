@@ -11,18 +11,13 @@ library's build (its sources and build id are its own, so the step library's pro
 fallback: without a HIP device the launch fails and the call raises.
 """
 import ctypes as C
-import os
+import functools
 import sys
 
+from . import _out
 from . import build as _build
+from ._out import _is
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-CSRC = os.path.join(HERE, 'csrc')
-LIB = os.path.join(HERE, 'libigw_relabel.so')
-SOURCES = [os.path.join(CSRC, 'relabel', 'igw_relabel.hip')]
-HEADERS = [os.path.join(CSRC, f) for f in ('igw_device.h', 'igw_trig.h', 'igw_trig_lut.h', 'igw_trig_tables.h',
-                                            'igw_vote.h')] + \
-          [os.path.join(HERE, '..', 'include', 'igw.h'), os.path.join(HERE, '..', 'include', 'igw_relabel.h')]
 VERSION = 1
 ROW = 1104          # bytes of a grid row
 CELLS = 1089
@@ -31,30 +26,22 @@ MAX_G = 256
 OUTPUTS = ('reward', 'done', 'progress', 'end', 'ret', 'target_size', 'target')   # in the order igw_relabel takes them
 DEFAULT = ('reward', 'done', 'end', 'ret')
 _vp, _i32, _i64, _f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_double
-# every symbol include/igw_relabel.h declares: (result, arguments)
-SIGNATURES = {
-    'igw_relabel_version': (C.c_int, []),
-    'igw_relabel_build_id': (C.c_char_p, []),
-    'igw_relabel_last_error': (C.c_char_p, []),
-    'igw_relabel': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _f64, _f64, _i32, _f64] + [_vp] * 8),
-}
-EXPORTS = list(SIGNATURES)
-LIBRARY = _build.Library(LIB, SOURCES, HEADERS, 'igw-relabel-build-id:', 'IGW_RELABEL_BUILD_ID', deps=[__file__])
-source_hash, built_id, is_stale = LIBRARY.source_hash, LIBRARY.built_id, LIBRARY.is_stale
 
 
 class RelabelError(RuntimeError):
     pass
 
 
-def build(force=False, verbose=False):
-    """Builds libigw_relabel.so; returns its path."""
-    return LIBRARY.build(force, verbose=verbose)
-
-
-BINDING = _build.Binding(LIBRARY, SIGNATURES, RelabelError, 'igw_relabel_last_error', 'igw_relabel_build_id',
-                         'gridworld_amd.relabel', 'igw_relabel')
+# include/igw_relabel.h declares igw_relabel and the three symbols every library has: (result, arguments)
+LIBRARY, BINDING = _build.query('relabel', __file__, {
+    'igw_relabel': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _f64, _f64, _i32, _f64] + [_vp] * 8),
+}, RelabelError, 'igw_relabel', headers=['igw_vote.h'])
+LIB, SOURCES, HEADERS = LIBRARY.lib, LIBRARY.sources, LIBRARY.headers
+SIGNATURES, EXPORTS = BINDING.signatures, list(BINDING.signatures)
+build, source_hash, built_id, is_stale = LIBRARY.build, LIBRARY.source_hash, LIBRARY.built_id, LIBRARY.is_stale
 load, check, build_id = BINDING.load, BINDING.check, BINDING.build_id
+check_outputs = functools.partial(_out.check_outputs, 'relabel', OUTPUTS)
+grid_rows = functools.partial(_out.grid_rows, 'relabel: grids')
 
 
 def relabel_into(records, n_records, first, length, starts, targets, at, e, g, l, right_scale, wrong_scale, max_steps,
@@ -67,41 +54,20 @@ def relabel_into(records, n_records, first, length, starts, targets, at, e, g, l
         BINDING.check(rc, 'igw_relabel')
 
 
-def check_outputs(outputs):
-    """The outputs named, in the library's order; ValueError for none or an unknown one."""
-    names = (outputs,) if isinstance(outputs, str) else tuple(outputs)
-    unknown = [k for k in names if k not in OUTPUTS]
-    if unknown or not names:
-        raise ValueError(f'relabel: outputs names one or more of {OUTPUTS}, got {outputs!r}')
-    return tuple(k for k in OUTPUTS if k in names)
-
-
 def _specs(e, g, l):
-    """name -> (shape, strides, elements per episode, dtype) of the tensor a caller sees."""
+    """name -> _out.spec of the tensor a caller sees: `target` is an [E, G, 9, 11, 11] view of 1104-byte rows (each in
+    the layout of `grid`), 16-byte aligned."""
     import torch
-    step = ((e, g, l), (g * l, l, 1), g * l)
-    pair = ((e, g), (g, 1), g)
-    return {'reward': step + (torch.float32,), 'done': step + (torch.uint8,), 'progress': step + (torch.int16,),
-            'end': pair + (torch.int32,), 'ret': pair + (torch.float32,), 'target_size': pair + (torch.int16,),
-            'target': ((e, g, 9, 11, 11), (g * ROW, ROW, 121, 11, 1), g * ROW, torch.int8)}
+    step = lambda dtype: _out.spec((e, g, l), dtype, (g * l, l, 1))  # noqa: E731
+    pair = lambda dtype: _out.spec((e, g), dtype, (g, 1))  # noqa: E731
+    return {'reward': step(torch.float32), 'done': step(torch.uint8), 'progress': step(torch.int16),
+            'end': pair(torch.int32), 'ret': pair(torch.float32), 'target_size': pair(torch.int16),
+            'target': _out.spec((e, g, 9, 11, 11), torch.int8, (g * ROW, ROW, 121, 11, 1), 16, (e, g * ROW))}
 
 
 def outputs(e, g, l, names, dev, stream=None):
-    """New tensors for the outputs `names`, as relabel() returns them: `target` is an [E, G, 9, 11, 11] view of 1104-byte
-    rows (each in the layout of `grid`)."""
-    import torch
-    res = {}
-    with torch.cuda.stream(stream):
-        for k in names:
-            shape, strides, row, dtype = _specs(e, g, l)[k]
-            res[k] = torch.as_strided(torch.empty((e, row), dtype=dtype, device=dev), shape, strides)
-    return res
-
-
-def _is(t, dtype, shape, dev):
-    import torch
-    return (torch.is_tensor(t) and t.dtype == dtype and tuple(t.shape) == tuple(shape) and t.device == dev
-            and t.is_contiguous())
+    """New tensors for the outputs `names`, as relabel() returns them."""
+    return _out.outputs('relabel', OUTPUTS, names, _specs(e, g, l), None, dev, stream)[0]
 
 
 def launch(records, first, length, starts, targets, at, pad, reward, gamma, names, out, dev, stream, alloc_stream=None):
@@ -141,42 +107,11 @@ def launch(records, first, length, starts, targets, at, pad, reward, gamma, name
         raise ValueError(f'relabel: max_steps must be 1..65534, got {max_steps}')
     if not math.isfinite(float(gamma)):
         raise ValueError(f'relabel: gamma must be finite, got {gamma}')
-    out = dict(out or {})
-    unknown = [k for k in out if k not in names]
-    if unknown:
-        raise ValueError(f'out holds {unknown}, the call writes {list(names)}')
-    specs = _specs(e, g, l)
-    for k, t in out.items():
-        shape, strides, _, dtype = specs[k]
-        if (not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dtype or t.device != dev
-                or (t.numel() > 0 and tuple(t.stride()) != strides) or (k == 'target' and t.data_ptr() % 16)):
-            raise ValueError(f'out[{k!r}] must be a {dtype} tensor {shape} with strides {strides} on {dev} (what relabel() '
-                             'returns; target 16-byte aligned)')
-    out.update(outputs(e, g, l, [k for k in names if k not in out], dev, alloc_stream))
-    ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+    res, ptrs = _out.outputs('relabel', OUTPUTS, names, _specs(e, g, l), out, dev, alloc_stream)
     if e:   # (the tensors of no episode have no address to pass)
         relabel_into(records.data_ptr(), records.numel() // RECORD, first.data_ptr(), length.data_ptr(), starts.data_ptr(),
-                     ptr(targets), ptr(at), e, g, l, right, wrong, max_steps, gamma,
-                     [out[k].data_ptr() if k in names else None for k in OUTPUTS], stream)
-    return {k: out[k] for k in names}
-
-
-def grid_rows(x, dev, lead):
-    """An integer tensor or array [*lead, 9, 11, 11], [*lead, 1089] or [*lead, 1104] -> a contiguous int8 device tensor
-    [*lead, 1104] (the one given, if it is that already)."""
-    import numpy as np
-    import torch
-    t = x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))
-    lead = tuple(lead)
-    if tuple(t.shape) == lead + (9, 11, 11):
-        t = t.reshape(lead + (CELLS,))
-    if tuple(t.shape) == lead + (ROW,):
-        return t.to(device=dev, dtype=torch.int8).contiguous()
-    if tuple(t.shape) != lead + (CELLS,):
-        raise ValueError(f'relabel: grids must be {lead + (9, 11, 11)}, {lead + (CELLS,)} or {lead + (ROW,)}, got {tuple(t.shape)}')
-    rows = torch.zeros(lead + (ROW,), dtype=torch.int8, device=dev)
-    rows[..., :CELLS] = t.to(device=dev, dtype=torch.int8)
-    return rows
+                     _out.ptr(targets), _out.ptr(at), e, g, l, right, wrong, max_steps, gamma, ptrs, stream)
+    return res
 
 
 def relabel(records, first, length, starts, targets=None, at=None, *, right_scale=1, wrong_scale=0.1, max_steps=250,

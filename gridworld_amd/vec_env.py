@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from . import aim as A
+from . import _queries as QR
 from . import codec as K
 from . import goal as G
 from . import peek as P
@@ -192,6 +192,14 @@ class _Rows:
                 if torch.is_tensor(t):
                     t.record_stream(self.stream)
 
+    def _query(self, rows, *args, out=None, also=()):
+        """One query call that returns a dict of tensors: marks `out`'s tensors (and `also`) as in use on the range's
+        stream, calls the adapter `rows` of _queries there, marks what it returns and returns it."""
+        self._in_use(*also, *(out or {}).values())
+        res = rows(self, *args, out, self._stream(), self.stream)
+        self._in_use(*res.values())
+        return res
+
     def _atlas(self):
         root = self._root()
         if root._render_atlas is None:
@@ -247,17 +255,17 @@ class _Rows:
 
     def _follow_mask(self, stream=None):
         if self._mask is not None:
-            _mask_rows(self, self._mask, False, None, self._stream() if stream is None else stream)
+            QR.mask_rows(self, self._mask, False, None, self._stream() if stream is None else stream)
 
     def _follow_goal(self, stream=None):
         if self._goal is not None:
-            _goal_rows(self, tuple(self._goal), self._goal, self._stream() if stream is None else stream,
-                       captured=stream is not None)
+            QR.goal_rows(self, tuple(self._goal), self._goal, self._stream() if stream is None else stream,
+                         captured=stream is not None)
 
     def _goal_scratch(self):
         """What gain=True needs beside its outputs, allocated once per range (on its stream) and kept, so that later
         calls allocate nothing: the mask and look tensors of igw_action_mask, a copy of the agent records and a mask
-        nobody reads (_goal_rows)."""
+        nobody reads (_queries.goal_rows)."""
         tmp = getattr(self, '_goal_tmp', None)
         if tmp is None:
             n, dev = self.num_envs, self.device
@@ -295,7 +303,7 @@ class _Rows:
         if stream is None:
             stream = self._stream()
             self._in_use(data)
-        _vox_rows(self, spec, data, restart, fill, self._goal, stream)
+        QR.vox_rows(self, spec, data, restart, fill, self._goal, stream)
 
     def step_walking_ptr(self, actions_i32):
         """Hot-loop variant: `actions_i32` is already a contiguous int32 device tensor [n], launched on the range's
@@ -330,7 +338,7 @@ class _Rows:
         result is the mask alone or the tuple (mask, look, actions) of what was asked for; with look / sample `out` may
         be the tuple of tensors to write.  Discrete(18) walking only: ValueError for flying and Dict-action envs."""
         self._in_use(*(out if isinstance(out, (tuple, list)) else (out,)))
-        res = _mask_rows(self, out, look, sample, self._stream(), self.stream)
+        res = QR.mask_rows(self, out, look, sample, self._stream(), self.stream)
         self._in_use(*(res if isinstance(res, tuple) else (res,)))
         return res
 
@@ -352,10 +360,7 @@ class _Rows:
         outside Discrete(18) walking and with size_reward=True (the wrapper's reward is not what is predicted)."""
         names = ('align', 'fit') + (('want',) if want else ()) + (('todo',) if todo else ()) + \
             (('gain', 'ends') if gain else ())
-        self._in_use(*(out or {}).values())
-        res = _goal_rows(self, names, out, self._stream(), self.stream)
-        self._in_use(*res.values())
-        return res
+        return self._query(QR.goal_rows, names, out=out)
 
     # ---- which cells a turn of the camera reaches (libigw_aim.so, include/igw_aim.h) ----
     def aim(self, max_turns=72, place=True, brk=True, out=None):
@@ -368,10 +373,7 @@ class _Rows:
         stream; `out`: a dict of planes to write, as an earlier call returned them; with every plane given nothing is
         allocated, so the call can be captured.  Discrete(18) walking only: ValueError for flying and Dict-action envs,
         for a max_turns outside 0..72 and with both planes off."""
-        self._in_use(*(out or {}).values())
-        res = _aim_rows(self, max_turns, place, brk, out, self._stream(), self.stream)
-        self._in_use(*res.values())
-        return res
+        return self._query(QR.aim_rows, max_turns, place, brk, out=out)
 
     # ---- K action sequences of H steps from the live state (libigw_peek.so, include/igw_peek.h) ----
     def peek(self, actions, gamma=1.0, outputs=P.OUTPUTS, out=None):
@@ -392,10 +394,7 @@ class _Rows:
         Discrete(18) walking, with size_reward=True (the wrapper's reward is not what is predicted), for K or H out of
         range, a wrong rank, a first dimension that is not N, and for empty or unknown outputs."""
         names = P.check_outputs(outputs)
-        self._in_use(*(out or {}).values())
-        res = _peek_rows(self, actions, gamma, names, out, self._stream(), self.stream)
-        self._in_use(*res.values())
-        return res
+        return self._query(QR.peek_rows, actions, gamma, names, out=out)
 
     # ---- ... of the flying and the walking Dict spaces (libigw_peek_dict.so, include/igw_peek_dict.h) ----
     def peek_dict(self, actions, gamma=1.0, outputs=PD.OUTPUTS, out=None):
@@ -415,10 +414,7 @@ class _Rows:
         for missing or extra keys, leading shapes that differ, K or H out of range, a wrong rank, a first dimension
         that is not N, and for empty or unknown outputs."""
         names = PD.check_outputs(outputs)
-        self._in_use(*(out or {}).values())
-        res = _peek_dict_rows(self, actions, gamma, names, out, self._stream(), self.stream)
-        self._in_use(*res.values())
-        return res
+        return self._query(QR.peek_dict_rows, actions, gamma, names, out=out)
 
     # ---- what every single-cell edit would be paid (libigw_worth.so, include/igw_worth.h) ----
     def worth(self, outputs=W.OUTPUTS, allow=None, stocked=False, out=None):
@@ -437,10 +433,7 @@ class _Rows:
         with every output given nothing is allocated, so the call can be captured.  Every action space; SizeReward's
         reward is not predicted.  ValueError for empty or unknown outputs, a wrong `out` and a wrong `allow`."""
         names = W.check_outputs(outputs)
-        self._in_use(allow, *(out or {}).values())
-        res = _worth_rows(self, names, allow, stocked, out, self._stream(), self.stream)
-        self._in_use(*res.values())
-        return res
+        return self._query(QR.worth_rows, names, allow, stocked, out=out, also=(allow,))
 
     # ---- rewards of logged episodes under other targets (libigw_relabel.so, include/igw_relabel.h) ----
     def relabel(self, goals='final', gamma=1.0, outputs=RL.DEFAULT, out=None):
@@ -463,10 +456,7 @@ class _Rows:
         changes the start.  ValueError without a log, for a range that holds no logged env, with size_reward=True, and
         for empty or unknown outputs or a wrong `out`."""
         names = RL.check_outputs(outputs)
-        self._in_use(*(out or {}).values())
-        res = _relabel_rows(self, goals, gamma, names, out, self._stream(), self.stream)
-        self._in_use(*res.values())
-        return res
+        return self._query(QR.relabel_rows, goals, gamma, names, out=out)
 
     # ---- voxel observations of logged transitions (libigw_recall.so, include/igw_recall.h) ----
     def recall(self, spec, batch=None, seed=0, episode=None, step=None, goals=None, goal=None, outputs=RCL.ENV_DEFAULT,
@@ -491,10 +481,7 @@ class _Rows:
         logged env, for 'want' / 'todo' planes, a 'target' plane without goals, and a wrong `out`."""
         spec, _ = RCL.spec_of(spec)
         names = RCL.check_outputs(outputs)
-        self._in_use(*(out or {}).values())
-        res = _recall_rows(self, spec, batch, seed, episode, step, goals, goal, names, out, self._stream(), self.stream)
-        self._in_use(*res.values())
-        return res
+        return self._query(QR.recall_rows, spec, batch, seed, episode, step, goals, goal, names, out=out)
 
     # ---- the state as the tensor a policy network reads (libigw_vox.so, include/igw_vox.h) ----
     def vox_obs(self, spec, out=None, restart=None, fill=False, goal=None):
@@ -511,7 +498,7 @@ class _Rows:
             with torch.cuda.stream(self.stream):
                 restart = torch.as_tensor(restart, device=self.device).ne(0).to(torch.uint8)
         self._in_use(out, restart, *(goal or {}).values())
-        res = _vox_rows(self, spec, out, restart, fill, goal, self._stream(), self.stream)
+        res = QR.vox_rows(self, spec, out, restart, fill, goal, self._stream(), self.stream)
         self._in_use(res)
         return res
 
@@ -682,7 +669,7 @@ class VecGridWorld(_Rows):
         if [k for k in goal if k not in ('want', 'todo', 'gain')]:
             raise ValueError(f"goal names 'want', 'todo' and / or 'gain', got {goal!r}")
         if 'gain' in goal:
-            _check_gain(mode != L.WALKING_DISCRETE, size_reward)
+            QR.check_gain(mode != L.WALKING_DISCRETE, size_reward)
             Q.load()
         held = None
         if goal:
@@ -1280,6 +1267,9 @@ class _Pov:
         return obs
 
 
+finished_episodes = QR.finished_episodes   # (tools/ read it from here)
+
+
 def _render_rows(env, out, channels, size, outputs, stream, alloc_stream=None):
     """One igw_render_pov launch (render.launch) over the state rows of a whole VecGridWorld or of a SubBatch."""
     agent, grid, occ = env._rows
@@ -1295,274 +1285,6 @@ def _render_obs_rows(env, spec, out, frame, restart, fill, stream, alloc_stream=
     n = env.num_envs
     return R.launch_obs((agent.data_ptr(), grid.data_ptr(), occ.data_ptr(), n), n, env.render_size, spec, out, frame,
                         restart, fill, env._atlas(), env.device, stream, alloc_stream)
-
-
-def _mask_rows(env, out, look, sample, stream, alloc_stream=None):
-    """One igw_action_mask launch (query.launch) over the state rows of a whole VecGridWorld or of a SubBatch."""
-    if env.flying or env.walk_dict:
-        raise ValueError('action_mask is defined for the Discrete(18) walking action space only (the flying and Dict '
-                         'actions turn the camera in the same step as they place)')
-    agent, _, occ = env._rows
-    return Q.launch(agent, occ, env.num_envs, env.select_and_place, out, look, sample, env.env_index_base, env.device,
-                    stream, alloc_stream)
-
-
-def _aim_rows(env, max_turns, place, brk, out, stream, alloc_stream=None):
-    """One igw_aim launch (aim.launch) over the state rows of a whole VecGridWorld or of a SubBatch."""
-    if env.flying or env.walk_dict:
-        raise ValueError('aim is defined for the Discrete(18) walking action space only (its turns are that space\'s '
-                         '5-degree camera actions)')
-    agent, _, occ = env._rows
-    return A.launch(agent, occ, env.num_envs, max_turns, place, brk, out, env.device, stream, alloc_stream)
-
-
-def _peek_rows(env, actions, gamma, names, out, stream, alloc_stream=None):
-    """One igw_peek launch (peek.launch) over the state rows of a whole VecGridWorld or of a SubBatch."""
-    if env.flying or env.walk_dict:
-        raise ValueError('peek is defined for the Discrete(18) walking action space only')
-    if env.cfg.size_reward:
-        raise ValueError('peek predicts the reward of the env itself; with size_reward=True the step returns '
-                         "SizeReward's (make the env with size_reward=False)")
-    if not torch.is_tensor(actions):
-        actions = np.asarray(actions)
-        if actions.dtype.kind not in 'iu':
-            raise ValueError(f'peek: actions must be integers, got {actions.dtype}')
-    elif actions.is_floating_point() or actions.is_complex() or actions.dtype == torch.bool:
-        raise ValueError(f'peek: actions must be integers, got {actions.dtype}')
-    P.shape_of(actions, env.num_envs)
-    if not (torch.is_tensor(actions) and actions.dtype == torch.int32 and actions.device == env.device
-            and actions.is_contiguous()):
-        with torch.cuda.stream(alloc_stream):
-            # (anything outside 0..17 is a no-op whatever its width: it becomes -1 before the narrowing, which would wrap a
-            # wide value into the range)
-            if torch.is_tensor(actions):
-                host = torch.where((actions < 0) | (actions > 17), torch.full_like(actions, -1), actions)
-            else:
-                host = torch.from_numpy(np.where((actions < 0) | (actions > 17), -1, actions).astype(np.int32))
-            actions = host.to(device=env.device, dtype=torch.int32).contiguous()
-    env._in_use(actions)
-    root, sl, cfg = env._root(), env._sl, env.cfg
-    agent, grid, occ = env._rows
-    state = [grid, occ, root.hist_buf[sl], root.aux_buf[sl], agent, root.task_target, root.task_start, root.task_meta,
-             root.task_index]
-    return P.launch(state, env.num_envs, actions, (cfg.right_placement_scale, cfg.wrong_placement_scale, cfg.max_steps,
-                                                   cfg.select_and_place), gamma, names, out, env.device, stream,
-                    alloc_stream)
-
-
-def _peek_dict_rows(env, actions, gamma, names, out, stream, alloc_stream=None):
-    """One igw_peek_flying / igw_peek_walking_dict launch (peek_dict.launch) over the state rows of a whole VecGridWorld
-    or of a SubBatch."""
-    if not (env.flying or env.walk_dict):
-        raise ValueError('peek_dict is defined for the flying and the walking Dict action spaces; in the Discrete(18) '
-                         'space call env.peek')
-    if env.cfg.size_reward:
-        raise ValueError('peek_dict predicts the reward of the env itself; with size_reward=True the step returns '
-                         "SizeReward's (make the env with size_reward=False)")
-    space = 'flying' if env.flying else 'walking_dict'
-    PD.shape_of(space, actions, env.num_envs)
-    root, sl, cfg = env._root(), env._sl, env.cfg
-    agent, grid, occ = env._rows
-    state = [grid, occ, root.hist_buf[sl], root.aux_buf[sl], agent, root.task_target, root.task_start, root.task_meta,
-             root.task_index]
-    res, bufs = PD.launch(space, state, env.num_envs, actions, (cfg.right_placement_scale, cfg.wrong_placement_scale,
-                                                                cfg.max_steps, cfg.select_and_place), gamma, names, out,
-                          env.device, stream, alloc_stream)
-    env._in_use(*bufs)
-    return res
-
-
-def _vox_rows(env, spec, out, restart, fill, goal, stream, alloc_stream=None):
-    """One igw_vox_obs launch (vox.launch) over the state rows of a whole VecGridWorld or of a SubBatch: 'grid' is the
-    range's grid rows, 'target' the task table's synthetic target plus its starting grid by task row, 'want' / 'todo'
-    the rows of `goal` (the dict goal() returned, or the range's persistent one)."""
-    lack = [k for k in spec.needs() if goal is None or k not in goal]
-    if lack:
-        raise ValueError(f"vox_obs: the planes {lack} are the goal query's: pass goal=env.goal(want=True, todo=True)")
-    root, sl, n = env._root(), env._sl, env.num_envs
-    agent, grid, _ = env._rows
-    sources = []
-    for name, _ in spec.planes:
-        if name == 'grid':
-            sources.append((grid.data_ptr(), None, L.GRID_STRIDE, 0))
-        elif name == 'target':
-            sources.append((root.task_target.data_ptr(), root.task_start.data_ptr(), L.GRID_STRIDE, 1))
-        else:
-            ptr, stride = X.rows_of(f'goal[{name!r}]', goal[name], n)
-            sources.append((ptr, None, stride, 0))
-    return X.launch(agent, root.aux_buf[sl], n, spec, sources, out, restart, fill, env.device, stream, alloc_stream)
-
-
-def _worth_rows(env, names, allow, stocked, out, stream, alloc_stream=None):
-    """One igw_worth launch (worth.launch) over the state rows of a whole VecGridWorld or of a SubBatch."""
-    root, sl, cfg = env._root(), env._sl, env.cfg
-    agent, _, _ = env._rows
-    state = [root.grid_buf[sl], root.hist_buf[sl], root.aux_buf[sl], agent, root.task_target, root.task_start,
-             root.task_meta, root.task_index]
-    return W.launch(state, env.num_envs, (cfg.right_placement_scale, cfg.wrong_placement_scale, cfg.max_steps), allow,
-                    stocked, names, out, env.device, stream, alloc_stream)
-
-
-def finished_episodes(heads, lo, cap):
-    """(first int64 [n], length int32 [n], task int64 [n], valid uint8 [n]) of the most recent finished episode of every
-    env of a slice heads[lo:lo + n] of the log's heads (include/igw.h: task row, steps recorded, episode number,
-    finished per slot): plain torch on the heads' device, nothing comes to the host."""
-    n = heads.shape[0]
-    fin = (heads[:, :, 3] != 0) & (heads[:, :, 1] > 0)
-    number = heads[:, :, 2].long() & 0xffffffff
-    score = torch.where(fin, number, torch.full_like(number, -1))
-    slot = score.argmax(1)
-    valid = score.gather(1, slot[:, None])[:, 0] >= 0
-    row = heads.gather(1, slot[:, None, None].expand(n, 1, 4))[:, 0]
-    length = torch.where(valid, row[:, 1].clamp(0, cap), torch.zeros_like(row[:, 1]))
-    task = torch.where(valid, row[:, 0], torch.zeros_like(row[:, 0])).long()
-    first = ((torch.arange(n, device=heads.device) + lo) * 2 + slot) * cap
-    return first, length.to(torch.int32), task, valid.to(torch.uint8)
-
-
-def _relabel_rows(env, goals, gamma, names, out, stream, alloc_stream=None):
-    """One igw_relabel launch (relabel.launch) over the logged envs of a whole VecGridWorld or of a SubBatch."""
-    root, cfg, dev = env._root(), env.cfg, env.device
-    if cfg.size_reward:
-        raise ValueError('relabel predicts the reward of the env itself; with size_reward=True the step returns '
-                         "SizeReward's (make the env with size_reward=False)")
-    if root._traj is None:
-        raise ValueError('relabel reads the episode log: call enable_trajectory_log() or make an EpisodeLogger first')
-    rec, heads, n_logged, cap = root._traj
-    lo, hi = env.lo, min(env.lo + env.num_envs, n_logged)
-    if hi <= lo:
-        raise ValueError(f'relabel: none of the envs [{env.lo}, {env.lo + env.num_envs}) is logged (the log holds the first {n_logged})')
-    e = hi - lo
-    with torch.cuda.stream(alloc_stream):
-        first, length, task, valid = finished_episodes(heads[lo:hi], lo, cap)
-        task = task.clamp(0, root.num_tasks - 1)
-        starts = root.task_start.index_select(0, task)
-        targets = at = None
-        if isinstance(goals, str):
-            if goals == 'final':
-                at = length[:, None].contiguous()
-            elif goals == 'own':
-                targets = (root.task_target.index_select(0, task) + starts)[:, None, :].contiguous()
-            else:
-                raise ValueError(f"relabel: goals is 'final', 'own', entries [E, G] or targets [E, G, 9, 11, 11], got {goals!r}")
-        else:
-            g = goals if torch.is_tensor(goals) else torch.as_tensor(np.asarray(goals))
-            if g.is_floating_point() or g.is_complex() or g.dtype == torch.bool:
-                raise ValueError(f'relabel: goals must be integers, got {g.dtype}')
-            if g.dim() == 2 and g.shape[0] == e:
-                at = g.to(device=dev, dtype=torch.int32).contiguous()
-            elif g.dim() in (3, 5) and g.shape[0] == e:
-                targets = RL.grid_rows(g, dev, (e, int(g.shape[1])))
-            else:
-                raise ValueError(f'relabel: goals must be entries [{e}, G] or targets [{e}, G, 9, 11, 11] / [{e}, G, 1104], '
-                                 f'got shape {tuple(g.shape)}')
-    env._in_use(first, length, starts, targets, at, valid)
-    res = RL.launch(rec, first, length, starts, targets, at, cap, (cfg.right_placement_scale, cfg.wrong_placement_scale,
-                                                                   cfg.max_steps), gamma, names, out, dev, stream, alloc_stream)
-    res.update(length=length, valid=valid)
-    return res
-
-
-def _recall_rows(env, spec, batch, seed, episode, step, goals, goal, names, out, stream, alloc_stream=None):
-    """One igw_recall launch (recall.launch) over the logged envs of a whole VecGridWorld or of a SubBatch."""
-    root, dev = env._root(), env.device
-    if root._traj is None:
-        raise ValueError('recall reads the episode log: call enable_trajectory_log() or make an EpisodeLogger first')
-    rec, heads, n_logged, cap = root._traj
-    lo, hi = env.lo, min(env.lo + env.num_envs, n_logged)
-    if hi <= lo:
-        raise ValueError(f'recall: none of the envs [{env.lo}, {env.lo + env.num_envs}) is logged (the log holds the first {n_logged})')
-    e = hi - lo
-    if (episode is None) != (step is None):
-        raise ValueError('recall: give episode and step together, or batch= alone')
-    if episode is None and (batch is None or isinstance(batch, bool) or int(batch) != batch or int(batch) < 0):
-        raise ValueError(f'recall: give batch=, the number of samples to draw, or episode= and step=, got batch={batch!r}')
-
-    def ints(name, x, dtype):
-        t = x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))
-        if t.is_floating_point() or t.is_complex() or t.dtype == torch.bool or t.dim() != 1:
-            raise ValueError(f'recall: {name} must be integers [B], got {t.dtype} {tuple(t.shape)}')
-        return t.to(device=dev, dtype=dtype).contiguous()
-    if goals is not None and not (isinstance(goals, dict) and 'target' in goals) and not (isinstance(goals, str) and goals == 'own'):
-        raise ValueError("recall: goals is None, 'own' or the dict relabel() returned with 'target', got "
-                         f'{goals if isinstance(goals, str) else type(goals).__name__!r}')
-    if goals is None and RCL.needs_goal(spec):
-        raise ValueError("recall: a 'target' plane shows the sample's goal: pass goals='own' or goals=env.relabel(..., "
-                         "outputs=(..., 'target'))")
-    if goal is not None and not isinstance(goals, dict):
-        raise ValueError('recall: goal= names a column of goals=r, the dict relabel() returned')
-    with torch.cuda.stream(alloc_stream):
-        first, length, task, _ = finished_episodes(heads[lo:hi], lo, cap)
-        task = task.clamp(0, root.num_tasks - 1)
-        starts = root.task_start.index_select(0, task)
-        init_pose = root.task_meta.index_select(0, task)[:, :40].contiguous().view(torch.float64)   # x, y, z, yaw, pitch
-        if episode is None:
-            episode, step = RCL.sample(length, int(batch), seed)
-        else:
-            episode, step = ints('episode', episode, torch.int32), ints('step', step, torch.int32)
-            if episode.shape != step.shape:
-                raise ValueError(f'recall: episode and step must have one length, got {tuple(episode.shape)}, {tuple(step.shape)}')
-        b = episode.shape[0]
-        rows, index, extra = None, None, {}
-        if isinstance(goals, str):
-            rows = root.task_target.index_select(0, task) + starts
-        elif isinstance(goals, dict):
-            rows = goals['target']
-            if not torch.is_tensor(rows) or rows.dim() != 5 or rows.shape[0] != e or rows.device != dev:
-                raise ValueError(f"recall: goals['target'] must be relabel()'s [{e}, G, 9, 11, 11] on {dev}")
-            n_g = int(rows.shape[1])
-            g = torch.zeros_like(episode, dtype=torch.int64) if goal is None else ints('goal', goal, torch.int64)
-            if g.shape != episode.shape:
-                raise ValueError(f'recall: goal must be [{b}], got {tuple(g.shape)}')
-            ep = episode.long()
-            inside = (ep >= 0) & (ep < e) & (g >= 0) & (g < n_g)
-            index = torch.where(inside, ep * n_g + g, torch.full_like(g, -1))
-            for k in ('reward', 'done'):
-                if k in goals:
-                    t = goals[k]
-                    if not torch.is_tensor(t) or t.dim() != 3 or tuple(t.shape[:2]) != (e, n_g) or t.device != dev:
-                        raise ValueError(f"recall: goals[{k!r}] must be relabel()'s [{e}, {n_g}, L] on {dev}")
-                    at = (step.long() - 1)
-                    ok = inside & (at >= 0) & (at < length.index_select(0, ep.clamp(0, e - 1)).clamp(max=t.shape[2]))
-                    got = t[ep.clamp(0, e - 1), g.clamp(0, n_g - 1), at.clamp(0, t.shape[2] - 1)]
-                    extra[k + '_relabel'] = torch.where(ok, got, torch.zeros_like(got))
-    env._in_use(first, length, starts, init_pose, episode, step, rows, index)
-    space = 'flying' if env.flying else 'walking_dict' if env.walk_dict else 'walking'
-    res = RCL.launch(rec, first, length, starts, init_pose, episode, step, spec, rows, index, cap, names, out, dev, stream,
-                     alloc_stream, space)
-    res.update(extra, episode=episode, step=step)
-    return res
-
-
-def _check_gain(other_space, size_reward):
-    if other_space:
-        raise ValueError('goal: gain is defined for the Discrete(18) walking action space only (the action mask it is '
-                         'built on is)')
-    if size_reward:
-        raise ValueError('goal: gain predicts the reward of the env itself; with size_reward=True the step returns '
-                         "SizeReward's (make the env with size_reward=False)")
-
-
-def _goal_rows(env, names, out, stream, alloc_stream=None, captured=False):
-    """One igw_goal launch (goal.launch) over the state rows of a whole VecGridWorld or of a SubBatch; with gain the two
-    igw_action_mask launches in front of it (_Rows.goal).  `captured`: the launch is part of a capture on `stream`,
-    which then is torch's current stream; otherwise the torch work goes to the range's stream."""
-    root, sl, cfg, mask, look = env._root(), env._sl, env.cfg, None, None
-    agent, _, occ = env._rows
-    if 'gain' in names:
-        _check_gain(env.flying or env.walk_dict, cfg.size_reward)
-        mask, look, full, spare = env._goal_scratch()
-        ask = lambda ag, m, lk: Q.action_mask_into(ag.data_ptr(), occ.data_ptr(), env.num_envs,  # noqa: E731
-                                                   env.select_and_place, m.data_ptr(), lk, None, 0, 0, 0, stream)
-        ask(agent, mask, None)
-        with torch.cuda.stream(None if captured else env.stream):
-            full.copy_(agent, non_blocking=True)
-            full.view(torch.int16)[:, 24:30].fill_(20)
-        ask(full, spare, look.data_ptr())
-    state = [root.grid_buf[sl], root.hist_buf[sl], root.aux_buf[sl], agent, root.task_target, root.task_start,
-             root.task_meta, root.task_index]
-    return G.launch(state, env.num_envs, (cfg.right_placement_scale, cfg.wrong_placement_scale, cfg.max_steps,
-                                          cfg.select_and_place), mask, look, names, out, env.device, stream, alloc_stream)
 
 
 def task_eval(targets, grids, full_grids=None, invariant=None, device='cuda:0'):

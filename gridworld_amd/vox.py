@@ -11,19 +11,14 @@ buffers (include/igw.h) and is not part of the step library's build (its sources
 library's profiles stay valid).  There is no CPU fallback: without a HIP device the launch fails and the call raises.
 """
 import ctypes as C
-import os
 import sys
 
 import numpy as np
 import torch
 
+from . import _out
 from . import build as _build
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-CSRC = os.path.join(HERE, 'csrc')
-LIB = os.path.join(HERE, 'libigw_vox.so')
-SOURCES = [os.path.join(CSRC, 'vox', 'igw_vox.hip')]
-HEADERS = [os.path.join(HERE, '..', 'include', 'igw_vox.h')]
 VERSION = 1
 MAX_SOURCES, MAX_STACK, MAX_RADIUS, CELLS, LEVELS = 4, 8, 10, 1089, 9
 ONEHOT, OCC = 0, 1
@@ -47,29 +42,17 @@ class Spec(C.Structure):
                 ('scale', C.c_float), ('bias', C.c_float), ('data', _vp), ('restart', _vp), ('restart_stride', _i64)]
 
 
-# every symbol include/igw_vox.h declares: (result, arguments)
-SIGNATURES = {
-    'igw_vox_version': (C.c_int, []),
-    'igw_vox_build_id': (C.c_char_p, []),
-    'igw_vox_last_error': (C.c_char_p, []),
-    'igw_vox_obs': (C.c_int, [_vp, _vp, _i32, C.POINTER(Spec), _vp]),
-}
-EXPORTS = list(SIGNATURES)
-LIBRARY = _build.Library(LIB, SOURCES, HEADERS, 'igw-vox-build-id:', 'IGW_VOX_BUILD_ID', deps=[__file__])
-source_hash, built_id, is_stale = LIBRARY.source_hash, LIBRARY.built_id, LIBRARY.is_stale
-
-
 class VoxError(RuntimeError):
     pass
 
 
-def build(force=False, verbose=False):
-    """Builds libigw_vox.so; returns its path."""
-    return LIBRARY.build(force, verbose=verbose)
-
-
-BINDING = _build.Binding(LIBRARY, SIGNATURES, VoxError, 'igw_vox_last_error', 'igw_vox_build_id',
-                         'gridworld_amd.vox', 'igw_vox_obs')
+# include/igw_vox.h declares igw_vox_obs and the three symbols every library has: (result, arguments)
+LIBRARY, BINDING = _build.query('vox', __file__, {
+    'igw_vox_obs': (C.c_int, [_vp, _vp, _i32, C.POINTER(Spec), _vp]),
+}, VoxError, 'igw_vox_obs', device=False)
+LIB, SOURCES, HEADERS = LIBRARY.lib, LIBRARY.sources, LIBRARY.headers
+SIGNATURES, EXPORTS = BINDING.signatures, list(BINDING.signatures)
+build, source_hash, built_id, is_stale = LIBRARY.build, LIBRARY.source_hash, LIBRARY.built_id, LIBRARY.is_stale
 load, check, build_id = BINDING.load, BINDING.check, BINDING.build_id
 
 
@@ -175,15 +158,8 @@ def launch(agent, aux, n, spec, sources, out, restart, fill, dev, stream, alloc_
     tensors' rows; `sources`: per plane of the spec (rows pointer, add pointer or None, row stride, by_task);
     `restart`: None or a 1-D uint8 / bool tensor of n elements on `dev`, at any stride.  With `out` nothing is
     allocated.  It touches the device only through data_ptr() and the ctypes call."""
-    shape = spec.shape(n)
-    if out is None:
-        with torch.cuda.stream(alloc_stream):
-            data = torch.empty(shape, dtype=spec.dtype, device=dev)
-    else:
-        data = out
-        if (not torch.is_tensor(data) or tuple(data.shape) != shape or data.dtype != spec.dtype or data.device != dev
-                or not data.is_contiguous()):
-            raise ValueError(f'out must be a contiguous {spec.dtype} tensor {shape} on {dev} (what vox_obs() returns)')
+    res, (data,) = _out.outputs('vox_obs', ('obs',), ('obs',), {'obs': _out.spec(spec.shape(n), spec.dtype)},
+                                None if out is None else {'obs': out}, dev, alloc_stream)
     ptr, stride = None, 0
     if restart is not None:
         if (not torch.is_tensor(restart) or restart.dtype not in (torch.uint8, torch.bool) or restart.dim() != 1
@@ -196,9 +172,9 @@ def launch(agent, aux, n, spec, sources, out, restart, fill, dev, stream, alloc_
     s.num_sources, s.agent_plane, s.frame, s.radius = len(spec.planes), int(spec.agent), FRAMES[spec.frame], spec.radius
     s.dtype, s.stack, s.fill, s.scale, s.bias = DTYPES[spec.dtype], spec.stack, int(bool(fill) or out is None), \
         spec.scale, spec.bias
-    s.data, s.restart, s.restart_stride = data.data_ptr(), ptr, stride
+    s.data, s.restart, s.restart_stride = data, ptr, stride
     vox_into(agent.data_ptr(), aux.data_ptr(), n, s, stream)
-    return data
+    return res['obs']
 
 
 if __name__ == '__main__':

@@ -11,18 +11,12 @@ own, so the step library's profiles stay valid).  There is no CPU fallback: with
 the call raises.
 """
 import ctypes as C
-import os
+import functools
 import sys
 
+from . import _out
 from . import build as _build
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-CSRC = os.path.join(HERE, 'csrc')
-LIB = os.path.join(HERE, 'libigw_worth.so')
-SOURCES = [os.path.join(CSRC, 'worth', 'igw_worth.hip')]
-HEADERS = [os.path.join(CSRC, f) for f in ('igw_device.h', 'igw_trig.h', 'igw_trig_lut.h', 'igw_trig_tables.h',
-                                            'igw_vote.h')] + \
-          [os.path.join(HERE, '..', 'include', 'igw.h'), os.path.join(HERE, '..', 'include', 'igw_worth.h')]
 VERSION = 1
 PLANES = 7
 ROW = 1104          # int16 words per env and plane
@@ -30,30 +24,21 @@ CELLS = 1089
 OUTPUTS = ('word', 'best')   # in the order igw_worth takes them
 worth_plane_names = ('break',) + tuple(f'place{k}' for k in range(1, 7))
 _vp, _i32, _f64 = C.c_void_p, C.c_int32, C.c_double
-# every symbol include/igw_worth.h declares: (result, arguments)
-SIGNATURES = {
-    'igw_worth_version': (C.c_int, []),
-    'igw_worth_build_id': (C.c_char_p, []),
-    'igw_worth_last_error': (C.c_char_p, []),
-    'igw_worth': (C.c_int, [_vp] * 8 + [_i32, _i32, _vp, _i32, _f64, _f64, _vp, _vp, _vp]),
-}
-EXPORTS = list(SIGNATURES)
-LIBRARY = _build.Library(LIB, SOURCES, HEADERS, 'igw-worth-build-id:', 'IGW_WORTH_BUILD_ID', deps=[__file__])
-source_hash, built_id, is_stale = LIBRARY.source_hash, LIBRARY.built_id, LIBRARY.is_stale
 
 
 class WorthError(RuntimeError):
     pass
 
 
-def build(force=False, verbose=False):
-    """Builds libigw_worth.so; returns its path."""
-    return LIBRARY.build(force, verbose=verbose)
-
-
-BINDING = _build.Binding(LIBRARY, SIGNATURES, WorthError, 'igw_worth_last_error', 'igw_worth_build_id',
-                         'gridworld_amd.worth', 'igw_worth')
+# include/igw_worth.h declares igw_worth and the three symbols every library has: (result, arguments)
+LIBRARY, BINDING = _build.query('worth', __file__, {
+    'igw_worth': (C.c_int, [_vp] * 8 + [_i32, _i32, _vp, _i32, _f64, _f64, _vp, _vp, _vp]),
+}, WorthError, 'igw_worth', headers=['igw_vote.h'])
+LIB, SOURCES, HEADERS = LIBRARY.lib, LIBRARY.sources, LIBRARY.headers
+SIGNATURES, EXPORTS = BINDING.signatures, list(BINDING.signatures)
+build, source_hash, built_id, is_stale = LIBRARY.build, LIBRARY.source_hash, LIBRARY.built_id, LIBRARY.is_stale
 load, check, build_id = BINDING.load, BINDING.check, BINDING.build_id
+check_outputs = functools.partial(_out.check_outputs, 'worth', OUTPUTS)
 
 
 def worth_into(state, n, max_steps, allow, stocked, right_scale, wrong_scale, word, best, stream):
@@ -65,32 +50,12 @@ def worth_into(state, n, max_steps, allow, stocked, right_scale, wrong_scale, wo
         BINDING.check(rc, 'igw_worth')
 
 
-def check_outputs(outputs):
-    """The outputs named, in the library's order; ValueError for none or an unknown one."""
-    names = (outputs,) if isinstance(outputs, str) else tuple(outputs)
-    unknown = [k for k in names if k not in OUTPUTS]
-    if unknown or not names:
-        raise ValueError(f'worth: outputs names one or more of {OUTPUTS}, got {outputs!r}')
-    return tuple(k for k in OUTPUTS if k in names)
-
-
 def _specs(n):
-    """name -> (shape, strides, row elements, dtype) of the tensor a caller sees; both are 16-byte aligned."""
+    """name -> _out.spec of the tensor a caller sees: `word` is an [n, 7, 9, 11, 11] view of seven 1104-word rows per env
+    (each in the layout of `grid`); both are 16-byte aligned."""
     import torch
-    return {'word': ((n, PLANES, 9, 11, 11), (PLANES * ROW, ROW, 121, 11, 1), PLANES * ROW, torch.int16),
-            'best': ((n, 4), (4, 1), 4, torch.int32)}
-
-
-def outputs(n, names, dev, stream=None):
-    """New tensors for the outputs `names`, as worth() returns them: `word` is an [n, 7, 9, 11, 11] view of seven
-    1104-word rows per env (each in the layout of `grid`)."""
-    import torch
-    res = {}
-    with torch.cuda.stream(stream):
-        for k in names:
-            shape, strides, row, dtype = _specs(n)[k]
-            res[k] = torch.as_strided(torch.empty((n, row), dtype=dtype, device=dev), shape, strides)
-    return res
+    return {'word': _out.spec((n, PLANES, 9, 11, 11), torch.int16, (PLANES * ROW, ROW, 121, 11, 1), 16, (n, PLANES * ROW)),
+            'best': _out.spec((n, 4), torch.int32, (4, 1), 16)}
 
 
 def launch(state, n, reward, allow, stocked, names, out, dev, stream, alloc_stream=None):
@@ -100,17 +65,6 @@ def launch(state, n, reward, allow, stocked, names, out, dev, stream, alloc_stre
     tensors to write, as an earlier call returned them; what it lacks is allocated.  It touches the device only
     through data_ptr() and the ctypes call."""
     import torch
-    out = dict(out or {})
-    unknown = [k for k in out if k not in names]
-    if unknown:
-        raise ValueError(f'out holds {unknown}, the call writes {list(names)}')
-    specs = _specs(n)
-    for k, t in out.items():
-        shape, strides, _, dtype = specs[k]
-        if (not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dtype or t.device != dev
-                or (n > 0 and tuple(t.stride()) != strides) or t.data_ptr() % 16):
-            raise ValueError(f'out[{k!r}] must be a {dtype} tensor {shape} with strides {strides} on {dev}, '
-                             '16-byte aligned (what worth() returns)')
     if allow is not None:
         ok = torch.is_tensor(allow) and allow.dtype == torch.uint8 and allow.device == dev and allow.data_ptr() % 16 == 0
         if ok and tuple(allow.shape) == (n, 2, 9, 11, 11):
@@ -120,12 +74,10 @@ def launch(state, n, reward, allow, stocked, names, out, dev, stream, alloc_stre
         if not ok:
             raise ValueError(f'allow must be a uint8 tensor on {dev}: [{n}, 2, 9, 11, 11] with 1104-byte rows (strides '
                              f'{(2 * ROW, ROW, 121, 11, 1)}) or contiguous [{n}, 2, {ROW}], 16-byte aligned')
-    out.update(outputs(n, [k for k in names if k not in out], dev, alloc_stream))
-    ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+    res, ptrs = _out.outputs('worth', OUTPUTS, names, _specs(n), out, dev, alloc_stream)
     right, wrong, max_steps = reward
-    worth_into([t.data_ptr() for t in state], n, max_steps, ptr(allow), stocked, right, wrong,
-               *[ptr(out.get(k)) for k in OUTPUTS], stream)
-    return {k: out[k] for k in OUTPUTS if k in names}
+    worth_into([t.data_ptr() for t in state], n, max_steps, _out.ptr(allow), stocked, right, wrong, *ptrs, stream)
+    return res
 
 
 def allow_from_aim(aim, out=None):

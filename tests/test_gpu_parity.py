@@ -449,5 +449,7 @@ def test_product_does_not_import_oracle():
     import inspect
     import gridworld_amd.vec_env as v
     import gridworld_amd._lib as l
-    for mod in (v, l, gridworld_amd):
+    import gridworld_amd._out as o
+    import gridworld_amd._queries as q
+    for mod in (v, l, o, q, gridworld_amd):
         assert 'oracle' not in inspect.getsource(mod).replace('no CPU fallback', '')

@@ -351,9 +351,9 @@ def test_out_writes_in_place_past_canary_rows_and_allocates_nothing(logs):
     at = torch.tensor([[T, 24, 0]] * E, dtype=torch.int32, device=dev)
     starts = env.task_start
     ref = G.relabel(rec, first, length, starts, at=at, outputs=ALL)
-    base = {k: torch.full((E + 2, row), 0x55, dtype=dt, device=dev) for k, (_, _, row, dt) in G.relabel._specs(E, g, CAP).items()}
-    out = {k: torch.as_strided(base[k], shape, strides, base[k].stride(0))
-           for k, (shape, strides, _, _) in G.relabel._specs(E, g, CAP).items()}
+    specs = G.relabel._specs(E, g, CAP)      # name -> (shape, strides, dtype, alignment, ...)
+    base = {k: torch.full((E + 2, strides[0]), 0x55, dtype=dt, device=dev) for k, (_, strides, dt, *_) in specs.items()}
+    out = {k: torch.as_strided(base[k], shape, strides, base[k].stride(0)) for k, (shape, strides, *_) in specs.items()}
     torch.cuda.synchronize()
     held = torch.cuda.memory_allocated(dev)
     again = G.relabel(rec, first, length, starts, at=at, outputs=ALL, out=out)

@@ -90,3 +90,52 @@ def test_a_touched_shared_header_makes_its_libraries_stale():
                 os.utime(SHARED[k], ns=(st.st_atime_ns, st.st_mtime_ns))
         assert not lib.is_stale(), name
         assert lib.built_id() == lib.source_hash()
+
+
+QUERIES = ('query', 'goal', 'aim', 'peek', 'peek_dict', 'vox', 'worth', 'relabel', 'recall')
+
+
+def test_every_query_module_describes_its_library_through_the_one_constructor():
+    """What build.query fills in for the nine modules: the three symbols every library has, in front of the module's own
+    entries; the library's names from the module's; and a staleness that sees the describing module and build.py."""
+    import ctypes
+    import importlib
+    from gridworld_amd import build as B
+    for name in QUERIES:
+        m = importlib.import_module('gridworld_amd.' + name)
+        sym = 'igw_' + name
+        assert {os.path.realpath(d) for d in m.LIBRARY.deps} == {os.path.realpath(m.__file__), os.path.realpath(B.__file__)}
+        assert list(m.SIGNATURES)[:3] == [sym + '_version', sym + '_build_id', sym + '_last_error'] and len(m.SIGNATURES) > 3
+        assert [m.SIGNATURES[k] for k in list(m.SIGNATURES)[:3]] == [(ctypes.c_int, []), (ctypes.c_char_p, []),
+                                                                     (ctypes.c_char_p, [])]
+        assert m.EXPORTS == list(m.SIGNATURES) and m.SIGNATURES is m.BINDING.signatures
+        assert m.BINDING.library is m.LIBRARY and m.BINDING.module == 'gridworld_amd.' + name
+        assert issubclass(m.BINDING.error, RuntimeError) and m.BINDING.error.__module__ == m.__name__
+        assert m.BINDING.what.startswith('igw_') and m.BINDING.what not in list(m.SIGNATURES)[:3]   # check()'s default entry
+        assert m.LIB == m.LIBRARY.lib == os.path.join(os.path.dirname(m.__file__), 'lib%s.so' % sym)
+        assert m.SOURCES == m.LIBRARY.sources == [os.path.join(CSRC, name, sym + '.hip')]
+        assert m.HEADERS is m.LIBRARY.headers and os.path.basename(m.HEADERS[-1]) == sym + '.h'
+        assert m.LIBRARY.marker == ('igw-%s-build-id:' % name.replace('_', '-')).encode()
+        assert m.LIBRARY.define == 'IGW_%s_BUILD_ID' % name.upper()
+        assert (m.build, m.source_hash, m.built_id, m.is_stale) == (m.LIBRARY.build, m.LIBRARY.source_hash,
+                                                                    m.LIBRARY.built_id, m.LIBRARY.is_stale)
+        assert (m.load, m.check, m.build_id) == (m.BINDING.load, m.BINDING.check, m.BINDING.build_id)
+        device = [os.path.basename(h) for h in B.DEVICE_HEADERS]
+        assert device == ['igw_device.h', 'igw_trig.h', 'igw_trig_lut.h', 'igw_trig_tables.h', 'igw.h']
+        assert ([h for h in m.HEADERS if h in B.DEVICE_HEADERS] == B.DEVICE_HEADERS) == (name not in ('vox', 'recall'))
+        assert all(os.path.exists(f) for f in m.SOURCES + m.HEADERS)
+
+
+def test_a_newer_describing_module_or_build_py_makes_a_library_stale():
+    from gridworld_amd import build as B, query as Q
+    Q.build()
+    assert not Q.is_stale()
+    for f in (Q.__file__, B.__file__):
+        st = os.stat(f)
+        later = max(os.stat(Q.LIB).st_mtime_ns, st.st_mtime_ns) + 10 ** 10
+        try:
+            os.utime(f, ns=(st.st_atime_ns, later))
+            assert Q.is_stale(), f
+        finally:
+            os.utime(f, ns=(st.st_atime_ns, st.st_mtime_ns))
+    assert not Q.is_stale()
