@@ -11,14 +11,13 @@
 //            word says.  The K + 1 entries lo .. t that the two stacks hold are then visited in order: each applies its
 //            own word (at most 8 of them, kept in LDS), is staged once and written to every slot of obs and next_obs that
 //            shows it.
-//   stage    Pose, head cell and heading quadrant are computed by every lane from the same words (the reset pose in
-//            binary64 for entry 0, the record's f32 agentPos widened for the others): no exchange.  Each lane walks output
-//            cells o = (y, u, w), maps them to the world cell they show and leaves one byte per plane in LDS, already in
-//            the output frame: for a one-hot plane 0 (empty, or outside the grid), 1..6 (the colour), 7 (any other
-//            value), for an occupancy plane [v != 0]; the agent's body is a plane of the second kind.
-//   write    A slot of C * 9 * S * S elements starts wherever the ones before it end.  It is cut at the ABSOLUTE 16-byte
-//            boundaries: a lane assembles a whole piece from the LDS planes and stores it with one non-temporal 16-byte
-//            store; the up to 15 bytes in front of the first boundary and behind the last go element by element.
+//   stage    The pose is the reset pose in binary64 for entry 0 and the record's f32 agentPos widened for the others,
+//            handed to every lane through LDS.  The channel table and the staging loop are csrc/igw_voxel_table.h and
+//            igw_voxel_stage.h, statements included in the kernel body and shared with the voxel observation; a plane's
+//            value at a world cell is the rebuilt grid's or the goal row's, both in LDS.
+//   write    The element, the frame of a pose and the writer of a slot at the absolute 16-byte boundaries are
+//            csrc/igw_voxel.h's, shared with the voxel observation too, where the stage / write story is told; the
+//            stores are non-temporal.
 //   A barrier separates the restaging of the planes from the previous entry's last reads of them.
 // A padding sample writes the value of bit 0 to both of its runs, zeros to its record and 0 to its valid byte.
 // Vector stores in plain C++ only.  Every loop is bounded by L, by the 64 lanes of a ballot or by the spec.
@@ -27,27 +26,25 @@
 #include <hip/hip_runtime.h>
 
 #include "../../../include/igw_recall.h"
+#include "../igw_voxel.h"
 
 namespace {
 
-constexpr int kThreads = 256;
+using namespace voxel;
+
+static_assert(IGW_RECALL_U8 == kU8 && IGW_RECALL_F16 == kF16 && IGW_RECALL_BF16 == kBF16 && IGW_RECALL_F32 == kF32, "element types");
+static_assert(IGW_RECALL_ONEHOT == kOneHot && IGW_RECALL_OCC == kOcc, "encodings");
+static_assert(IGW_RECALL_LEVELS == kLevels && IGW_RECALL_MAX_RADIUS == kMaxRadius && IGW_RECALL_MAX_PLANES == kMaxSources, "limits");
 constexpr int kWave = 64;
-constexpr int kLevels = IGW_RECALL_LEVELS;
 constexpr int kRow = IGW_RECALL_ROW;
 constexpr int kCells = IGW_RECALL_CELLS;
 constexpr int kRecord = IGW_RECALL_RECORD;
 constexpr int kChunks = kRow / 16;                               // 69 dwordx4 of a grid row
-constexpr int kMaxSide = 2 * IGW_RECALL_MAX_RADIUS + 1;
-constexpr int kMaxPlane = kLevels * kMaxSide * kMaxSide;         // cells of the largest window: 3,969
-constexpr int kPlanes = IGW_RECALL_MAX_PLANES + 1;               // the spec's planes and the agent's
-constexpr int kTable = 32;                                       // >= 4 * 6 + 1 channels, and one behind the last
-constexpr int kOther = 7;                                        // a non-zero value outside 1..6
+constexpr int kPlanes = kMaxSources + 1;                         // the spec's planes and the agent's
 constexpr int kChangeOffset = 40;                                // the u16 `change` of a trajectory record
 constexpr int kNone = 0xffff;
 static_assert(kCells == 16 * (kChunks - 1) + 1, "the last chunk of a row holds one cell");
 static_assert(kCells <= 0x7ff, "a cell fits the low 11 bits of a change");
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 struct RecallParams {
     void* obs;
@@ -70,105 +67,12 @@ struct RecallParams {
     int32_t nplanes, agent_plane, ego, R, dtype, stack, channels;
 };
 
-template <int kDtype> struct Elem { using E = uint16_t; };
-template <> struct Elem<IGW_RECALL_U8> { using E = uint8_t; };
-template <> struct Elem<IGW_RECALL_F32> { using E = uint32_t; };
-
-// b = 0 / 1 as the bits of an element: u8 as it is; the float types from (float)b * scale, then + bias (two roundings:
-// the library is built with -ffp-contract=off), f16 / bf16 rounded to nearest-even from that f32.
-template <int kDtype>
-__device__ __forceinline__ typename Elem<kDtype>::E value(uint32_t b, float scale, float bias) {
-    if constexpr (kDtype == IGW_RECALL_U8) {
-        return (uint8_t)b;
-    } else {
-        float f = (float)b * scale;
-        f = f + bias;
-        const uint32_t u = __float_as_uint(f);
-        if constexpr (kDtype == IGW_RECALL_F32) {
-            return u;
-        } else if constexpr (kDtype == IGW_RECALL_F16) {
-            const _Float16 h = (_Float16)f;
-            return __builtin_bit_cast(uint16_t, h);
-        } else {   // (scale and bias are finite, so f is no NaN unless inf - inf: kept a quiet NaN)
-            if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)0x7fc0u;
-            return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-        }
-    }
-}
-
-__device__ __forceinline__ void store16(void* p, u32x4 v) { __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(p)); }
-
-// rint(v) as an int, clamped to +-64: a centre that far out sees only cells outside the grid, as any farther one does
-__device__ __forceinline__ int cell_of(double v) {
-    const double r = __builtin_rint(v);
-    return (int)__builtin_fmin(__builtin_fmax(r, -64.0), 64.0);
-}
-
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
 // A value every lane loaded from the same address, as the scalar it is
 __device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 __device__ __forceinline__ int64_t uniform64(int64_t v) {
     return (int64_t)(((uint64_t)(uint32_t)uniform((int)(v >> 32)) << 32) | (uint32_t)uniform((int)v));
-}
-
-// How a run of L elements at `base` is cut at the absolute 16-byte boundaries: `head` elements in front of the first,
-// `pieces` whole 16-byte pieces, and the rest from `tail` on.
-template <typename E> struct Cut {
-    int head, pieces, tail;
-    __device__ __forceinline__ Cut(const E* base, int L) {
-        constexpr int P = 16 / (int)sizeof(E);
-        const unsigned lead = (16u - (unsigned)(reinterpret_cast<uintptr_t>(base) & 15u)) & 15u;
-        head = min(L, (int)(lead / sizeof(E)));
-        pieces = (L - head) / P;
-        tail = head + pieces * P;
-    }
-};
-
-struct Planes {
-    const uint8_t* cells;      // [kPlanes][kMaxPlane] bytes in LDS
-    const uint8_t* ch_plane;   // [kTable]
-    const uint8_t* ch_match;   // [kTable]: the channel is [code == it]
-    int P9;                    // cells of one channel: 9 * S * S
-};
-
-// The staged planes into one slot of L elements.
-template <int kDtype>
-__device__ __forceinline__ void write_slot(typename Elem<kDtype>::E* base, int L, const Planes& pl,
-                                           typename Elem<kDtype>::E v0, typename Elem<kDtype>::E v1) {
-    using E = typename Elem<kDtype>::E;
-    constexpr int P = 16 / (int)sizeof(E);
-    const int tid = threadIdx.x;
-    const Cut<E> cut(base, L);
-    const int rounds = (L / P + kThreads) / kThreads;   // >= pieces / kThreads, from the spec alone
-#pragma unroll 1
-    for (int it = 0; it < rounds; it++) {
-        const int p = tid + it * kThreads;
-        if (p >= cut.pieces) continue;
-        const int e0 = cut.head + p * P;
-        const int ch = e0 / pl.P9, o = e0 - ch * pl.P9;
-        // A piece lies in one channel or straddles two: its first `own` elements are channel ch's from cell o on, the
-        // others channel ch + 1's from cell 0 on (behind the last channel the table still answers, and no piece reaches
-        // there).
-        const int own = pl.P9 - o;
-        const int at1 = (int)pl.ch_plane[ch] * kMaxPlane + o, at2 = (int)pl.ch_plane[ch + 1] * kMaxPlane - own;
-        const uint32_t m1 = pl.ch_match[ch], m2 = pl.ch_match[ch + 1];
-        uint32_t w[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-        for (int j = 0; j < P; j++) {
-            const bool next = j >= own;
-            const uint32_t code = pl.cells[(next ? at2 : at1) + j];
-            const uint32_t e = code == (next ? m2 : m1) ? v1 : v0;
-            w[j * (int)sizeof(E) / 4] |= e << (8 * ((j * (int)sizeof(E)) & 3));
-        }
-        store16(base + e0, u32x4{w[0], w[1], w[2], w[3]});
-    }
-    const int edge = cut.head + (L - cut.tail);   // < 2 * P
-    if (tid < edge) {
-        const int e = tid < cut.head ? tid : cut.tail + (tid - cut.head);
-        const int ch = e / pl.P9, o = e - ch * pl.P9;
-        base[e] = pl.cells[(int)pl.ch_plane[ch] * kMaxPlane + o] == pl.ch_match[ch] ? v1 : v0;
-    }
 }
 
 // `n` elements of the value v0 from `base` on: a padding sample's run.
@@ -182,7 +86,7 @@ __device__ __forceinline__ void fill_run(E* base, int n, E v0) {
     if constexpr (sizeof(E) == 2) w *= 0x00010001u;
     const u32x4 v{w, w, w, w};
 #pragma unroll 1
-    for (int p = tid; p < cut.pieces; p += kThreads) store16(base + cut.head + p * P, v);
+    for (int p = tid; p < cut.pieces; p += kThreads) store16<true>(base + cut.head + p * P, v);
     const int edge = cut.head + (n - cut.tail);
     if (tid < edge) base[tid < cut.head ? tid : cut.tail + (tid - cut.head)] = v0;
 }
@@ -198,7 +102,7 @@ template <int kDtype>
 __device__ __forceinline__ void emit_padding(const RecallParams& p, int64_t b, int P9) {
     using E = typename Elem<kDtype>::E;
     const int n = p.stack * p.channels * P9;   // <= 8 * 25 * 3,969
-    const E v0 = value<kDtype>(0u, p.scale, p.bias);
+    const E v0 = elem_value<kDtype>(0u, p.scale, p.bias);
     if (p.obs) fill_run<E>(static_cast<E*>(p.obs) + b * n, n, v0);
     if (p.next_obs) fill_run<E>(static_cast<E*>(p.next_obs) + b * n, n, v0);
 }
@@ -207,20 +111,29 @@ __device__ __forceinline__ void emit_padding(const RecallParams& p, int64_t b, i
 template <int kDtype>
 __device__ __forceinline__ void emit_entry(const RecallParams& p, int64_t b, int t, int s, const Planes& pl) {
     using E = typename Elem<kDtype>::E;
-    const E v0 = value<kDtype>(0u, p.scale, p.bias), v1 = value<kDtype>(1u, p.scale, p.bias);
+    const E v0 = elem_value<kDtype>(0u, p.scale, p.bias), v1 = elem_value<kDtype>(1u, p.scale, p.bias);
     const int K = p.stack, L = p.channels * pl.P9;
     E* obs = p.obs ? static_cast<E*>(p.obs) + b * K * (int64_t)L : nullptr;
     E* next = p.next_obs ? static_cast<E*>(p.next_obs) + b * K * (int64_t)L : nullptr;
 #pragma unroll 1
     for (int j = 0; j < K; j++) {   // (block-uniform conditions)
-        if (obs && max(0, t - K + j) == s) write_slot<kDtype>(obs + (int64_t)j * L, L, pl, v0, v1);
-        if (next && max(0, t - K + 1 + j) == s) write_slot<kDtype>(next + (int64_t)j * L, L, pl, v0, v1);
+        if (obs && max(0, t - K + j) == s) write_slot<kDtype, true>(obs + (int64_t)j * L, L, pl, v0, v1);
+        if (next && max(0, t - K + 1 + j) == s) write_slot<kDtype, true>(next + (int64_t)j * L, L, pl, v0, v1);
     }
 }
 
 __device__ __forceinline__ int source_of(uint32_t planes, int k) { return (int)((planes >> (2 * k)) & 1u); }
 __device__ __forceinline__ int encoding_of(uint32_t planes, int k) { return (int)((planes >> (2 * k + 1)) & 1u); }
 static_assert(IGW_RECALL_GOAL == 1 && IGW_RECALL_OCC == 1, "a plane's source and encoding are a bit each");
+
+// What igw_voxel_table.h and igw_voxel_stage.h take from this kernel: a plane's value is the rebuilt grid's or the goal
+// row's, both in LDS.
+#define VOXEL_PLANES p.nplanes
+#define VOXEL_AGENT p.agent_plane
+#define VOXEL_ENCODING(k) encoding_of(p.planes, k)
+#define VOXEL_EGO p.ego
+#define VOXEL_GUARD_CELL 1
+#define VOXEL_READ(k, c, v) const int v = source_of(p.planes, k) == IGW_RECALL_GOAL ? (int)goal_row[c] : (int)grid[c];
 
 // One kernel per element type: the type decides the stores, and four of them in one kernel cost scalar registers.
 template <int kDtype>
@@ -266,26 +179,7 @@ __global__ __launch_bounds__(kThreads) void igw_recall_kernel(const RecallParams
     if (p.valid && tid == 0) p.valid[b] = 1;
 
     // ---- channel -> (plane, test); the starting row, the goal row, the entries' own words
-    if (tid < kTable) {
-        int plane = 0, match = 0, first = 0;
-#pragma unroll
-        for (int s = 0; s < IGW_RECALL_MAX_PLANES; s++) {
-            if (s < p.nplanes) {
-                const int count = encoding_of(p.planes, s) == IGW_RECALL_ONEHOT ? 6 : 1;
-                if (tid >= first && tid < first + count) {
-                    plane = s;
-                    match = encoding_of(p.planes, s) == IGW_RECALL_ONEHOT ? tid - first + 1 : 1;
-                }
-                first += count;
-            }
-        }
-        if (p.agent_plane && tid == first) {
-            plane = p.nplanes;
-            match = 1;
-        }
-        ch_plane[tid] = (uint8_t)plane;
-        ch_match[tid] = (uint8_t)match;
-    }
+#include "../igw_voxel_table.h"
     if (tid < kChunks) {
         u32x4 v = reinterpret_cast<const u32x4*>(p.start + sm.e * kRow)[tid];
         uint32_t w[4] = {v.x, v.y, v.z, v.w};
@@ -348,36 +242,8 @@ __global__ __launch_bounds__(kThreads) void igw_recall_kernel(const RecallParams
         }
         __syncthreads();   // the grid is entry s's; the previous entry's planes and pose have been read
 
-        const double px = pose_s[0], py = pose_s[1], pz = pose_s[2], yaw = pose_s[3];
-        const int hx = cell_of(px) + 5, hy = cell_of(py) + 1, hz = cell_of(pz) + 5;
-        const double f = __builtin_floor((yaw + 45.0) / 90.0);
-        const int q = (int)(f - 4.0 * __builtin_floor(f / 4.0)) & 3;
-        const int fx = (q == 1) - (q == 3), fz = (q == 2) - (q == 0), rx = (q == 0) - (q == 2), rz = (q == 1) - (q == 3);
-#pragma unroll 1
-        for (int o = tid; o < P9; o += kThreads) {
-            const int y = o / SS, rem = o - y * SS, u = rem / S, w = rem - u * S;
-            int x = u, z = w;
-            if (p.ego) {
-                const int sa = R - u, tr = w - R;
-                x = hx + sa * fx + tr * rx;
-                z = hz + sa * fz + tr * rz;
-            }
-            const bool inside = (unsigned)x < 11u && (unsigned)z < 11u;
-            const int c = inside ? y * 121 + x * 11 + z : 0;
-#pragma unroll
-            for (int k = 0; k < IGW_RECALL_MAX_PLANES; k++) {
-                if (k < p.nplanes) {
-                    int code = 0;
-                    if (inside) {
-                        const int v = source_of(p.planes, k) == IGW_RECALL_GOAL ? (int)goal_row[c] : (int)grid[c];
-                        code = encoding_of(p.planes, k) == IGW_RECALL_OCC ? v != 0 : v >= 1 && v <= 6 ? v : v != 0 ? kOther : 0;
-                    }
-                    cells[k * kMaxPlane + o] = (uint8_t)code;
-                }
-            }
-            if (p.agent_plane)
-                cells[p.nplanes * kMaxPlane + o] = (uint8_t)(inside && x == hx && z == hz && (y == hy || y == hy - 1));
-        }
+        const Frame fr(pose_s[0], pose_s[1], pose_s[2], pose_s[3]);
+#include "../igw_voxel_stage.h"
         __syncthreads();
 
         emit_entry<kDtype>(p, b, t, s, pl);

@@ -8,8 +8,10 @@
 
 The library is a separate one, as the renderer's, the codec's and the other queries' are: it reads trajectory records
 (include/igw.h: igw_set_trajectory_log), starting grids, reset poses and goal rows, no env state, and is not part of the
-step library's build (its sources and build id are its own, so the step library's profiles stay valid).  There is no
-CPU fallback: without a HIP device the launch fails and the call raises.
+step library's build (its sources and build id are its own, so the step library's profiles stay valid); the element,
+the frame of a pose, the staging of the planes and the slot writer (csrc/igw_voxel.h, igw_voxel_table.h,
+igw_voxel_stage.h) it shares with the voxel observation's library.  There is no CPU fallback: without a HIP device the
+launch fails and the call raises.
 """
 import ctypes as C
 import functools
@@ -54,7 +56,7 @@ class RecallError(RuntimeError):
 LIBRARY, BINDING = _build.query('recall', __file__, {
     'igw_recall': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _i64, _i64, _vp,
                              C.POINTER(Spec), _vp, _vp, _vp, _vp, _vp]),
-}, RecallError, 'igw_recall', device=False)
+}, RecallError, 'igw_recall', headers=['igw_voxel.h', 'igw_voxel_table.h', 'igw_voxel_stage.h'], device=False)
 LIB, SOURCES, HEADERS = LIBRARY.lib, LIBRARY.sources, LIBRARY.headers
 SIGNATURES, EXPORTS = BINDING.signatures, list(BINDING.signatures)
 build, source_hash, built_id, is_stale = LIBRARY.build, LIBRARY.source_hash, LIBRARY.built_id, LIBRARY.is_stale

@@ -8,7 +8,9 @@
 
 The library is a separate one, as the renderer's, the codec's and the queries' are: it reads the step path's state
 buffers (include/igw.h) and is not part of the step library's build (its sources and build id are its own, so the step
-library's profiles stay valid).  There is no CPU fallback: without a HIP device the launch fails and the call raises.
+library's profiles stay valid); the element, the frame of a pose, the staging of the planes and the slot writer
+(csrc/igw_voxel.h, igw_voxel_table.h, igw_voxel_stage.h) it shares with the recall query's library.  There is no CPU
+fallback: without a HIP device the launch fails and the call raises.
 """
 import ctypes as C
 import sys
@@ -49,7 +51,7 @@ class VoxError(RuntimeError):
 # include/igw_vox.h declares igw_vox_obs and the three symbols every library has: (result, arguments)
 LIBRARY, BINDING = _build.query('vox', __file__, {
     'igw_vox_obs': (C.c_int, [_vp, _vp, _i32, C.POINTER(Spec), _vp]),
-}, VoxError, 'igw_vox_obs', device=False)
+}, VoxError, 'igw_vox_obs', headers=['igw_voxel.h', 'igw_voxel_table.h', 'igw_voxel_stage.h'], device=False)
 LIB, SOURCES, HEADERS = LIBRARY.lib, LIBRARY.sources, LIBRARY.headers
 SIGNATURES, EXPORTS = BINDING.signatures, list(BINDING.signatures)
 build, source_hash, built_id, is_stale = LIBRARY.build, LIBRARY.source_hash, LIBRARY.built_id, LIBRARY.is_stale

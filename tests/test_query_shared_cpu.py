@@ -1,5 +1,5 @@
 """The code the query libraries share (csrc/igw_vote.h: the histogram vote; csrc/peek/igw_peek_core.h and igw_peek_body.h:
-the peek kernel):
+the peek kernel; csrc/igw_voxel.h, igw_voxel_table.h and igw_voxel_stage.h: the back end of the two voxel writers):
 each shared function is defined once outside the step library, and every library that includes a shared header lists it
 among its HEADERS, so that its build id and its staleness see the header.  No device."""
 import os
@@ -9,9 +9,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'gridworld_amd', 'csrc')
 STEP_ONLY = ('igw_kernels.hip', 'igw_device.h')      # the step library restates what it needs: nothing moves out of it
 SHARED = {'igw_vote.h': os.path.join(CSRC, 'igw_vote.h'), 'igw_peek_core.h': os.path.join(CSRC, 'peek', 'igw_peek_core.h'),
-          'igw_peek_body.h': os.path.join(CSRC, 'peek', 'igw_peek_body.h')}
+          'igw_peek_body.h': os.path.join(CSRC, 'peek', 'igw_peek_body.h'), 'igw_voxel.h': os.path.join(CSRC, 'igw_voxel.h'),
+          'igw_voxel_table.h': os.path.join(CSRC, 'igw_voxel_table.h'),
+          'igw_voxel_stage.h': os.path.join(CSRC, 'igw_voxel_stage.h')}
+VOXEL = {'igw_voxel.h', 'igw_voxel_table.h', 'igw_voxel_stage.h'}
+PEEK = {'igw_vote.h', 'igw_peek_core.h', 'igw_peek_body.h'}
 ONCE = ('class1', 'row_piece_max', 'vote_change', 'wave_sum_i32', 'world_act_pre', 'world_act_post', 'finish_break',
-        'world_update', 'syn_size_delta', 'finish_step')
+        'world_update', 'syn_size_delta', 'finish_step', 'elem_value', 'store16', 'pose_cell', 'write_slot')
 
 
 def _code(path):
@@ -50,6 +54,24 @@ def test_every_shared_function_is_defined_once_outside_the_step_library():
     assert not set(SHARED) & {os.path.basename(f) for f in _included(os.path.join(CSRC, 'igw_kernels.hip'))}
 
 
+def test_the_voxel_channel_table_and_staging_loop_are_shared_text():
+    """The channel table and the staging loop of vox and recall are statements in two files that both kernels include in
+    their bodies: each file is included once by each kernel, and what marks the table (the six channels of a one-hot
+    plane) and the loop (the ahead / right mapping of the agent's frame, the 0 / 1..6 / kOther classification, the agent's
+    body) stands in those files and nowhere else under csrc."""
+    files = [os.path.join(d, f) for d, _, fs in os.walk(CSRC) for f in fs]
+    marks = {'igw_voxel_table.h': (r'tid\s*-\s*first\s*\+\s*1', r'match\s*=', r'ch_plane\s*\[\s*tid\s*\]\s*='),
+             'igw_voxel_stage.h': (r'fr\.hx\s*\+\s*\w+\s*\*\s*fr\.fx', r'kOther\s*:\s*0', r'y\s*==\s*fr\.hy\s*-\s*1',
+                                   r'\*\s*121\s*\+\s*x\s*\*\s*11\s*\+\s*z')}
+    for name, pats in marks.items():
+        for kernel in (os.path.join(CSRC, 'vox', 'igw_vox.hip'), os.path.join(CSRC, 'recall', 'igw_recall.hip')):
+            included = re.findall(r'#include "\.\./(igw_voxel_(?:table|stage)\.h)"', _code(kernel))
+            assert included.count(name) == 1, (kernel, name)
+        for pat in pats:
+            where = [os.path.basename(f) for f in files if re.search(pat, _code(f))]
+            assert where == [name], (pat, where)
+
+
 def _users():
     """library name -> the shared headers its sources include."""
     users = {}
@@ -64,7 +86,7 @@ def _users():
 def test_a_library_lists_the_shared_headers_it_includes():
     users, libs = _users(), _libraries()
     assert users == {'goal': {'igw_vote.h'}, 'worth': {'igw_vote.h'}, 'relabel': {'igw_vote.h'},
-                     'peek': set(SHARED), 'peek_dict': set(SHARED)}
+                     'peek': PEEK, 'peek_dict': PEEK, 'vox': VOXEL, 'recall': VOXEL}
     for name, mine in users.items():
         listed = {os.path.realpath(libs[name].path(h)) for h in libs[name].headers}
         for k in mine:

@@ -44,21 +44,26 @@ def test_vox_library_cross_compiles_and_exports_its_declared_symbols():
 
 
 def test_vox_sources_are_in_no_other_library():
-    """The vox library's files enter no other library's build id and no other library's files enter its own; it is
+    """The vox library's files enter no other library's build id and no other library's files enter its own, but for
+    csrc/igw_voxel.h, igw_voxel_table.h and igw_voxel_stage.h, which are vox's and recall's and no other library's; it is
     built with the step library's flags."""
-    from gridworld_amd import aim as A, build as B, codec as K, goal as G, peek as P, query as Q, render as R, vox as X
+    from gridworld_amd import aim as A, build as B, codec as K, goal as G, peek as P, query as Q, recall as RC, render as R, \
+        vox as X
     others = B.SOURCES + B.HEADERS + R.SOURCES + R.HEADERS + R.OBS_SOURCES + R.OBS_HEADERS + Q.SOURCES + Q.HEADERS + \
         K.LIBRARY.sources + K.LIBRARY.headers + G.SOURCES + G.HEADERS + A.SOURCES + A.HEADERS + P.SOURCES + P.HEADERS
     srcs = {os.path.basename(s) for s in others}
     mine = [os.path.basename(s) for s in X.SOURCES + X.HEADERS]
-    assert sorted(mine) == ['igw_vox.h', 'igw_vox.hip']
+    shared = ['igw_voxel.h', 'igw_voxel_stage.h', 'igw_voxel_table.h']
+    assert sorted(mine) == ['igw_vox.h', 'igw_vox.hip'] + shared
     assert not srcs & set(mine)
+    assert {os.path.basename(s) for s in RC.SOURCES + RC.HEADERS} & set(mine) == set(shared)
     assert X.LIBRARY.flags == () and os.path.basename(X.LIB) == 'libigw_vox.so'
     assert X.LIBRARY.marker == b'igw-vox-build-id:'
     assert X.LIBRARY.marker not in (Q.LIBRARY.marker, G.LIBRARY.marker, A.LIBRARY.marker, P.LIBRARY.marker,
                                     B.STEP.marker, R.LIBRARY.marker, R.OBS_LIBRARY.marker)
     text = open(X.SOURCES[0]).read()
-    assert re.findall(r'#include "([^"]+)"', text) == ['../../../include/igw_vox.h']
+    assert re.findall(r'#include "([^"]+)"', text) == ['../../../include/igw_vox.h', '../igw_voxel.h', '../igw_voxel_table.h',
+                                                        '../igw_voxel_stage.h']
 
 
 def test_vox_code_object_has_no_scratch_and_no_vector_spills(tmp_path):
