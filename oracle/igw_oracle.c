@@ -86,6 +86,9 @@ struct igo_env {
     float obs_compass;
     double reward;
     int done;
+#ifdef IGO_CENSUS
+    int census_best[4]; /* argmax (dx, dz, rot) of the episode's previous recount, [3]: there was one */
+#endif
 };
 
 static inline int cell(int y, int x, int z) { return (y * IGO_GRID_X + x) * IGO_GRID_Z + z; }
@@ -117,19 +120,47 @@ enum {
     CB_AGENT_IN_ZONE, CB_AGENT_RING,       /* the agent's cell after a step: in the zone / in the padding ring */
     CB_AGENT_BEYOND,                       /* [x<-6, x>6, z<-6, z>6] */
     CB_AGENT_ABOVE = CB_AGENT_BEYOND + 4, CB_AGENT_BELOW, CB_AGENT_OFF_GROUND, CB_AGENT_TERMINAL_VELOCITY,
+    /* the reward path (tests/reward_cases.py): everything from here on is a "reward bin" */
+    CB_REWARD_FIRST,
+    CB_SYN_ID = CB_REWARD_FIRST,           /* [synthetic id -6..-1, 1..6] */
+    CB_SYN_CANCELLED = CB_SYN_ID + 12, CB_SYN_EMPTY,
+    CB_SYN_TOP,                            /* [highest level of the synthetic target 0..8] */
+    CB_SYN_LEVEL_FULL = CB_SYN_TOP + 9,
+    CB_ADM_ONLY_IDENTITY, CB_ADM_ALL_121, CB_ADM_X_ONLY, CB_ADM_Z_ONLY, CB_ADM_ROTATIONS_DIFFER,
+    CB_USER_NARROWS, CB_USER_NOT_INVARIANT,
+    CB_CHANGE_PLACE,                       /* [grid level 0..8] */
+    CB_CHANGE_BREAK = CB_CHANGE_PLACE + 9, /* [grid level 0..8] */
+    CB_CHANGE_SYN = CB_CHANGE_BREAK + 9,   /* place_empty, break_placed, break_start, restore_start, recolour_start, break_recoloured */
+    CB_VOTES_NONE = CB_CHANGE_SYN + 6, CB_VOTES_GAIN_ONLY, CB_VOTES_LOSE_ONLY, CB_VOTES_BOTH, CB_VOTES_121,
+    CB_VOTES_LEVEL,                        /* [grid level 0..8 of a change that casts or withdraws a vote] */
+    CB_VOTES_ID = CB_VOTES_LEVEL + 9,      /* [synthetic id -6..-1, 1..6 of such a vote] */
+    CB_CACHE_STALE_KEPT = CB_VOTES_ID + 12, CB_CACHE_STALE_EQUAL, CB_CACHE_UP, CB_CACHE_DOWN,
+    CB_RIGHT,                              /* <= -2, -1, 0, +1, >= +2 */
+    CB_WRONG = CB_RIGHT + 5,               /* -1, 0, +1 */
+    CB_BEST_ROT = CB_WRONG + 3,            /* [rotation 0..3] */
+    CB_BEST_SHIFT = CB_BEST_ROT + 4,       /* x_neg, x_pos, z_neg, z_pos */
+    CB_BEST_EXTREME = CB_BEST_SHIFT + 4,
+    CB_BEST_EXTREME_ROT,                   /* [rotation 0..3] */
+    CB_BEST_MOVES = CB_BEST_EXTREME_ROT + 4, CB_BEST_TIE, CB_BEST_DROP_UNIQUE, CB_BEST_DROP_SHARED,
+    CB_DONE_ROT,                           /* [rotation 0..3] */
+    CB_DONE_SHIFTED = CB_DONE_ROT + 4, CB_DONE_AT_MAX_STEPS, CB_DONE_EMPTY, CB_DONE_MAX_STEPS_ONLY,
+    CB_SIZE_PAYS, CB_SIZE_ZERO,
     CB_COUNT
 };
 static int64_t census[CB_COUNT];
 static const void* census_fall_env; /* env whose supporting block was just broken */
+/* the cell grid_set is about to write: its env, its index, the synthetic id before and after */
+static struct { const void* env; int cell, before, after; } census_ch;
 
-void igo_census_reset(void) { memset(census, 0, sizeof(census)); census_fall_env = NULL; }
+void igo_census_reset(void) { memset(census, 0, sizeof(census)); census_fall_env = NULL; census_ch.env = NULL; }
+int igo_census_first_reward_bin(void) { return CB_REWARD_FIRST; }
 int igo_census_read(int64_t* out) {
     if (out) memcpy(out, census, sizeof(census));
     return CB_COUNT;
 }
 /* bin names, one per line, in index order */
 const char* igo_census_names(void) {
-    static char buf[8192];
+    static char buf[16384];
     static const char* side[6] = {"top", "bottom", "xlo", "xhi", "zlo", "zhi"};
     static const char* face[6] = {"up", "down", "xneg", "xpos", "zpos", "zneg"};
     static const char* wall[6] = {"xlo", "xhi", "zlo", "zhi", "floor", "ceiling"};
@@ -149,6 +180,27 @@ const char* igo_census_names(void) {
     p += sprintf(p, "agent.in_zone\nagent.padding_ring\nagent.beyond.xlo\nagent.beyond.xhi\nagent.beyond.zlo\n"
                     "agent.beyond.zhi\nagent.above_level8\nagent.below_level-4\nagent.off_ground_plane\n"
                     "agent.terminal_velocity\n");
+    for (int c = -6; c <= 6; c++) if (c) p += sprintf(p, "syn.id.%d\n", c);
+    p += sprintf(p, "syn.cancelled_cell\nsyn.empty\n");
+    for (int y = 0; y < 9; y++) p += sprintf(p, "syn.top_level.%d\n", y);
+    p += sprintf(p, "syn.level_full\nadm.only_identity\nadm.all_121\nadm.x_only\nadm.z_only\nadm.rotations_differ\n"
+                    "user.full_grid_narrows\nuser.not_invariant\n");
+    for (int y = 0; y < 9; y++) p += sprintf(p, "change.place.level%d\n", y);
+    for (int y = 0; y < 9; y++) p += sprintf(p, "change.break.level%d\n", y);
+    p += sprintf(p, "change.syn.place_empty\nchange.syn.break_placed\nchange.syn.break_start\nchange.syn.restore_start\n"
+                    "change.syn.recolour_start\nchange.syn.break_recoloured\n"
+                    "votes.none\nvotes.gain_only\nvotes.lose_only\nvotes.both\nvotes.121\n");
+    for (int y = 0; y < 9; y++) p += sprintf(p, "votes.level%d\n", y);
+    for (int c = -6; c <= 6; c++) if (c) p += sprintf(p, "votes.id.%d\n", c);
+    p += sprintf(p, "cache.stale_kept\ncache.stale_equal\ncache.catches_up.up\ncache.catches_up.down\n"
+                    "right.le-2\nright.-1\nright.0\nright.+1\nright.ge+2\nwrong.-1\nwrong.0\nwrong.+1\n");
+    for (int r = 0; r < 4; r++) p += sprintf(p, "best.rot%d\n", r);
+    p += sprintf(p, "best.shift.x_neg\nbest.shift.x_pos\nbest.shift.z_neg\nbest.shift.z_pos\nbest.shift.extreme\n");
+    for (int r = 0; r < 4; r++) p += sprintf(p, "best.shift.extreme.rot%d\n", r);
+    p += sprintf(p, "best.moves\nbest.tie\nbest.drop_unique\nbest.drop_shared\n");
+    for (int r = 0; r < 4; r++) p += sprintf(p, "done.complete.rot%d\n", r);
+    p += sprintf(p, "done.complete.shifted\ndone.complete_at_max_steps\ndone.empty_task\ndone.max_steps_only\n"
+                    "size_reward.pays\nsize_reward.zero\n");
     return buf;
 }
 #ifdef IGO_CENSUS_GCOV
@@ -401,6 +453,163 @@ void igo_task_eval(const int8_t* target, const int8_t* full_grid, int invariant,
     free(t);
 }
 
+/* --------------------------------------------------- census of the reward path
+ * (tests/reward_cases.py).  Same rules as above: compiled in with -DIGO_CENSUS only, all counting in census_*
+ * functions that restate what the task functions decide (and may call them), so a --coverage build of the task
+ * functions sees no extra branch. */
+#ifdef IGO_CENSUS
+static int census_adm_count(const igo_task* t, int i) {
+    int n = 0;
+    for (int k = 0; k < 441; k++) n += t->adm[i][k];
+    return n;
+}
+/* admissibility of a rotation-invariant task */
+static void census_adm(const igo_task* t) {
+    if (t->n_rot != 4) return;
+    int n = census_adm_count(t, 0), off_x = 0, off_z = 0;
+    for (int k = 0; k < 441; k++)
+        if (t->adm[0][k]) { off_x += k / 21 != 10; off_z += k % 21 != 10; }
+    if (n == 1) census[CB_ADM_ONLY_IDENTITY]++;
+    if (n == 121) census[CB_ADM_ALL_121]++;
+    if (n > 1 && n < 441 && off_x == 0) census[CB_ADM_X_ONLY]++; /* spans 11 along x: only dz moves */
+    if (n > 1 && n < 441 && off_z == 0) census[CB_ADM_Z_ONLY]++;
+    if (memcmp(t->adm[0], t->adm[1], 441) != 0) census[CB_ADM_ROTATIONS_DIFFER]++;
+}
+static void census_user(const igo_env* e, const int8_t* target, const int8_t* full_grid, int invariant) {
+    if (!invariant) { census[CB_USER_NOT_INVARIANT]++; return; }
+    census_adm(&e->user);
+    if (full_grid) {
+        igo_task* own = (igo_task*)malloc(sizeof(igo_task));
+        int with = 0, without = 0;
+        task_init(own, target, NULL, 1);
+        for (int i = 0; i < 4; i++) { with += census_adm_count(&e->user, i); without += census_adm_count(own, i); }
+        if (with < without) census[CB_USER_NARROWS]++;
+        free(own);
+    }
+}
+/* the synthetic task igo_reset has just built */
+static void census_syn(igo_env* e, const int8_t* syn_target) {
+    int top = -1;
+    e->census_best[3] = 0;
+    for (int y = 0; y < IGO_GRID_Y; y++) {
+        int per_id[13] = {0};
+        for (int k = 0; k < 121; k++) {
+            int i = y * 121 + k, c = syn_target[i];
+            if (c != 0) { census[CB_SYN_ID + (c < 0 ? c + 6 : c + 5)]++; top = y; per_id[c + 6]++; }
+            if (e->target[i] != 0 && e->target[i] == e->init[i]) census[CB_SYN_CANCELLED]++;
+        }
+        for (int c = 0; c < 13; c++) if (per_id[c] == 121) census[CB_SYN_LEVEL_FULL]++;
+    }
+    if (top < 0) census[CB_SYN_EMPTY]++;
+    else census[CB_SYN_TOP + top]++;
+    census_adm(&e->synth);
+}
+/* grid_set is about to write `kind` into the cell at pos (if it lies in the zone) */
+static void census_change(const igo_env* e, const int* pos, int kind) {
+    if (pos[0] < -5 || pos[0] > 5 || pos[2] < -5 || pos[2] > 5 || pos[1] < -1 || pos[1] >= 8) return;
+    int y = pos[1] + 1, i = cell(y, pos[0] + 5, pos[2] + 5);
+    int g0 = e->grid[i], s = e->init[i], gain = 0, lose = 0;
+    int a = (int8_t)(g0 - s), b = (int8_t)(kind - s);
+    const int8_t* level = e->synth.grids[0] + y * 121;
+    census[(kind != 0 ? CB_CHANGE_PLACE : CB_CHANGE_BREAK) + y]++;
+    if (kind != 0) census[CB_CHANGE_SYN + (s == 0 ? 0 : kind == s ? 3 : 4)]++;
+    else census[CB_CHANGE_SYN + (s == 0 ? 1 : g0 == s ? 2 : 5)]++;
+    for (int k = 0; k < 121; k++) { gain += b != 0 && level[k] == b; lose += a != 0 && level[k] == a; }
+    census[gain ? (lose ? CB_VOTES_BOTH : CB_VOTES_GAIN_ONLY) : (lose ? CB_VOTES_LOSE_ONLY : CB_VOTES_NONE)]++;
+    if (gain == 121 || lose == 121) census[CB_VOTES_121]++;
+    if (gain || lose) census[CB_VOTES_LEVEL + y]++;
+    if (gain) census[CB_VOTES_ID + (b < 0 ? b + 6 : b + 5)]++;
+    if (lose) census[CB_VOTES_ID + (a < 0 ? a + 6 : a + 5)]++;
+    census_ch.env = e; census_ch.cell = i; census_ch.before = a; census_ch.after = b;
+}
+/* task_get_intersection of every admissible alignment at once (-1: not admissible), counted from the blocks: a grid
+   cell (y, xg, zg) and a target cell (y, xt, zt) of the same id meet under the translation (xt - xg, zt - zg) */
+static void census_counts(const igo_task* t, const int8_t* grid, int* n) {
+    for (int k = 0; k < t->n_rot * 441; k++) n[k] = t->adm[k / 441][k % 441] ? 0 : -1;
+    for (int g = 0; g < IGO_CELLS; g++) {
+        if (grid[g] == 0) continue;
+        int y = g / 121, xg = g / 11 % 11, zg = g % 11;
+        for (int i = 0; i < t->n_rot; i++)
+            for (int c = 0; c < 121; c++)
+                if (t->grids[i][y * 121 + c] == grid[g]) {
+                    int k = i * 441 + (c / 11 - xg + 10) * 21 + (c % 11 - zg + 10);
+                    if (n[k] >= 0) n[k]++;
+                }
+    }
+}
+/* after task_step_intersection: syn is the synthetic grid it saw, cached the task's max_int before it */
+static void census_step(igo_env* e, const int8_t* syn, int right, int wrong, int cached, double reward) {
+    static int nb[4 * 441], na[4 * 441];
+    const igo_task* t = &e->synth;
+    int changed = census_ch.env == e;
+    int task_done = t->max_int == t->target_size;
+    census_ch.env = NULL;
+    census[CB_RIGHT + (right <= -2 ? 0 : right >= 2 ? 4 : right + 2)]++;
+    census[CB_WRONG + wrong + 1]++;
+    if (e->cfg.size_reward) census[reward > 0 ? CB_SIZE_PAYS : CB_SIZE_ZERO]++;
+    if (t->target_size == 0 && task_done) census[CB_DONE_EMPTY]++;
+    if (!task_done && e->step_no == e->cfg.max_steps) census[CB_DONE_MAX_STEPS_ONLY]++;
+    if (!changed) return;
+    /* every admissible alignment's count before and after the change, in the reference's iteration order */
+    int8_t before[IGO_CELLS];
+    int mb = 0, ma = 0, at_mb = 0, at_ma = 0, first = -1, lowered = 0;
+    memcpy(before, syn, IGO_CELLS);
+    before[census_ch.cell] = (int8_t)census_ch.before;
+    census_counts(t, before, nb);
+    census_counts(t, syn, na);
+    for (int k = 0; k < t->n_rot * 441; k++) {
+        if (nb[k] > mb) mb = nb[k];
+        if (na[k] > ma) ma = na[k];
+    }
+    for (int k = 0; k < t->n_rot * 441; k++) {
+        if (nb[k] == mb && mb > 0) { at_mb++; lowered += na[k] < nb[k]; }
+        if (na[k] == ma && ma > 0) { at_ma++; if (first < 0) first = k; }
+    }
+    if (lowered && at_mb == 1) census[CB_BEST_DROP_UNIQUE]++;
+    if (lowered && lowered < at_mb) census[CB_BEST_DROP_SHARED]++;
+    if (wrong == 0) { /* the block count stood still: the task kept its cached max_int */
+        census[t->max_int != ma ? CB_CACHE_STALE_KEPT : CB_CACHE_STALE_EQUAL]++;
+        return;
+    }
+    if (ma != t->max_int) abort(); /* census_counts restates task_get_intersection: a recount must agree with it */
+    if (mb > cached) census[CB_CACHE_UP]++;
+    if (mb < cached) census[CB_CACHE_DOWN]++;
+    if (ma == 0) return;
+    int dx = first % 441 / 21 - 10, dz = first % 21 - 10, rot = first / 441, far_x = 0, far_z = 0;
+    for (int k = 0; k < 441; k++)
+        if (t->adm[rot][k]) {
+            if (abs(k / 21 - 10) > far_x) far_x = abs(k / 21 - 10);
+            if (abs(k % 21 - 10) > far_z) far_z = abs(k % 21 - 10);
+        }
+    census[CB_BEST_ROT + rot]++;
+    if (dx < 0) census[CB_BEST_SHIFT + 0]++;
+    if (dx > 0) census[CB_BEST_SHIFT + 1]++;
+    if (dz < 0) census[CB_BEST_SHIFT + 2]++;
+    if (dz > 0) census[CB_BEST_SHIFT + 3]++;
+    if ((far_x > 0 && abs(dx) == far_x) || (far_z > 0 && abs(dz) == far_z)) { census[CB_BEST_EXTREME]++; census[CB_BEST_EXTREME_ROT + rot]++; }
+    if (at_ma > 1) census[CB_BEST_TIE]++;
+    if (e->census_best[3] && (e->census_best[0] != dx || e->census_best[1] != dz || e->census_best[2] != rot))
+        census[CB_BEST_MOVES]++;
+    e->census_best[0] = dx; e->census_best[1] = dz; e->census_best[2] = rot; e->census_best[3] = 1;
+    if (task_done && t->target_size > 0) {
+        census[CB_DONE_ROT + rot]++;
+        if (dx != 0 || dz != 0) census[CB_DONE_SHIFTED]++;
+        if (e->step_no == e->cfg.max_steps) census[CB_DONE_AT_MAX_STEPS]++;
+    }
+}
+#define CENSUS_USER(e, target, full, inv) census_user(e, target, full, inv);
+#define CENSUS_SYN(e, syn) census_syn(e, syn);
+#define CENSUS_CHANGE(e, pos, kind) census_change(e, pos, kind);
+#define CENSUS_CACHED(t) int census_cached = (t)->max_int;
+#define CENSUS_STEP(e, syn, right, wrong, reward) census_step(e, syn, right, wrong, census_cached, reward);
+#else
+#define CENSUS_USER(e, target, full, inv)
+#define CENSUS_SYN(e, syn)
+#define CENSUS_CHANGE(e, pos, kind)
+#define CENSUS_CACHED(t)
+#define CENSUS_STEP(e, syn, right, wrong, reward)
+#endif
+
 /* ----------------------------------------------------------------- World */
 
 /* core/world.py:57-58 */
@@ -568,6 +777,7 @@ static void update(igo_env* e, double dt) {
 
 /* env.py:136-153 callbacks keep the dense grid in sync */
 static void grid_set(igo_env* e, const int* pos, int kind) {
+    CENSUS_CHANGE(e, pos, kind)
     if (build_zone(pos[0], pos[1], pos[2], 0))
         e->grid[cell(pos[1] + 1, pos[0] + 5, pos[2] + 5)] = (int8_t)kind;
 }
@@ -656,6 +866,7 @@ void igo_set_task(igo_env* e, const int8_t* target, const int8_t* start, const i
     else memset(e->init, 0, IGO_CELLS); /* None is treated as [] */
     task_init(&e->user, target, full_grid, invariant);
     e->have_task = 1;
+    CENSUS_USER(e, target, full_grid, invariant)
 }
 
 void igo_set_initial_pose(igo_env* e, const double* p) {
@@ -681,6 +892,7 @@ void igo_reset(igo_env* e) {
     for (int i = 0; i < IGO_CELLS; i++) syn_target[i] = (int8_t)(e->target[i] - e->init[i]);
     task_init(&e->synth, syn_target, NULL, 1);
     task_reset(&e->synth, NULL, 0);
+    CENSUS_SYN(e, syn_target)
     /* remove placed blocks, add the starting ones, env.py:234-238 */
     memcpy(e->grid, e->init, IGO_CELLS);
     e->pos[0] = e->initial_position[0]; e->pos[1] = e->initial_position[1];
@@ -708,6 +920,7 @@ static void finish_step(igo_env* e) {
     e->obs_agentPos[3] = (float)e->rot[1];
     e->obs_agentPos[4] = (float)e->rot[0];
     for (int i = 0; i < IGO_CELLS; i++) syn[i] = (int8_t)(e->grid[i] - e->init[i]);
+    CENSUS_CACHED(&e->synth)
     task_step_intersection(&e->synth, syn, &right, &wrong, &done);
     done = done || (e->step_no == e->cfg.max_steps);
     double reward;
@@ -722,6 +935,7 @@ static void finish_step(igo_env* e) {
     }
     e->reward = reward;
     e->done = done;
+    CENSUS_STEP(e, syn, right, wrong, reward)
 }
 
 /* core/world.py:360-394 */
@@ -884,6 +1098,9 @@ static void* job_run(void* arg) {
 }
 
 static void run_jobs(job_t* proto, int64_t n, int nthreads, int64_t* steps, int64_t* changed) {
+#ifdef IGO_CENSUS
+    nthreads = 1; /* the counters and the changed-cell record are plain globals, whatever the caller asks for */
+#endif
     if (nthreads < 1) nthreads = 1;
     if (nthreads > 256) nthreads = 256;
     if ((int64_t)nthreads > n) nthreads = n > 0 ? (int)n : 1;

@@ -31,6 +31,9 @@ CFLAGS = ['-fPIC', '-std=c11', '-ffp-contract=off', '-fno-fast-math', '-pthread'
 STEP_FUNCTIONS = ('build_zone', 'world_lookup', 'normalize', 'hit_test', 'get_sight_vector', 'get_motion_vector',
                   'collide', 'update_substep', 'update', 'grid_set', 'place_or_remove_block', 'world_step', 'igo_reset',
                   'finish_step', 'igo_step_walking', 'igo_step_walking_dict', 'igo_step_flying')
+# the reward path's census (tests/reward_cases.py) reads these as well; a tuple of its own, so that the step census
+# (profiles/r15_step_census.json) stays what it was
+TASK_FUNCTIONS = ('task_init', 'task_get_intersection', 'task_maximal_intersection', 'task_reset', 'task_step_intersection')
 
 
 class Census:
@@ -55,31 +58,43 @@ class Census:
         assert self.O is not product and self.lib is not product.lib()
         self.lib.igo_census_names.restype = C.c_char_p
         self.lib.igo_census_read.argtypes = [C.c_void_p]
-        self.names = self.lib.igo_census_names().decode().split('\n')[:-1]
-        assert len(self.names) == self.lib.igo_census_read(None) == len(set(self.names))
+        names = self.lib.igo_census_names().decode().split('\n')[:-1]
+        assert len(names) == self.lib.igo_census_read(None) == len(set(names))
+        first = self.lib.igo_census_first_reward_bin()
+        self.names, self.reward_names = names[:first], names[first:]    # the step path's bins, the reward path's
         self.lib.igo_census_reset()
 
-    def bins(self):
-        """{bin name: count} since the library was loaded."""
-        out = np.zeros(len(self.names), np.int64)
+    def _read(self):
+        out = np.zeros(len(self.names) + len(self.reward_names), np.int64)
         self.lib.igo_census_read(out.ctypes.data_as(C.c_void_p))
-        return dict(zip(self.names, (int(v) for v in out)))
+        return [int(v) for v in out]
+
+    def bins(self):
+        """{bin name: count} of the step path's bins since the library was loaded."""
+        return dict(zip(self.names, self._read()))
+
+    def reward_bins(self):
+        """{bin name: count} of the reward path's bins since the library was loaded."""
+        return dict(zip(self.reward_names, self._read()[len(self.names):]))
 
     def unreached_bins(self):
         return sorted(k for k, v in self.bins().items() if v == 0)
 
-    def branches(self):
-        """{'function | source line | branch k': times taken} of STEP_FUNCTIONS, everything run so far."""
+    def unreached_reward_bins(self):
+        return sorted(k for k, v in self.reward_bins().items() if v == 0)
+
+    def branches(self, functions=STEP_FUNCTIONS):
+        """{'function | source line | branch k': times taken} of `functions`, everything run so far."""
         assert self.coverage
         self.lib.igo_census_flush()
         subprocess.run(['gcov', '-b', '-c', 'igw_oracle.o'], check=True, cwd=self.dir, stdout=subprocess.DEVNULL)
-        return parse_gcov(os.path.join(self.dir, 'igw_oracle.c.gcov'))
+        return parse_gcov(os.path.join(self.dir, 'igw_oracle.c.gcov'), functions)
 
     def unreached_branches(self):
         return sorted(k for k, v in self.branches().items() if v == 0)
 
 
-def parse_gcov(path):
+def parse_gcov(path, functions=STEP_FUNCTIONS):
     out, func, line, k = {}, None, None, 0
     for row in open(path):
         m = re.match(r'function (\w+) called', row)
@@ -91,13 +106,13 @@ def parse_gcov(path):
             line, k = ' '.join(m.group(2).split()), 0
             continue
         m = re.match(r'branch\s+\d+ (never executed|taken (\d+))', row)
-        if m and func in STEP_FUNCTIONS:
+        if m and func in functions:
             key = f'{func} | {line} | branch {k}'
             assert key not in out, key
             out[key] = int(m.group(2) or 0)
         if m:
             k += 1
-    assert len({k.split(' | ')[0] for k in out}) >= 12   # (normalize, get_sight_vector and the like have no branch)
+    assert len({k.split(' | ')[0] for k in out}) >= min(12, len(functions))   # (normalize, get_sight_vector and the like have no branch)
     return out
 
 
